@@ -11,7 +11,15 @@ rasterizer's forward + backward), backpropagates a fixed upstream dL/dcolor into
 accumulate over the rank's views, as train.py sums view losses), and for N > 1 all-reduces (SUM)
 the gradients over RCCL.  Inputs are resident in HBM before timing.
 
-Also reported (untimed for `value`, ``call_site``): ms per view of train.py's whole render call
+A plain run does only what ``value`` needs: set up, warm up, time ``--steps`` steps, print the
+result line.  ``--dump-outputs DIR`` also writes what the last timed step computed (the step's rendered
+images and the gradients it left on the leaves; C5: the fitted parameters) as ``DIR/<name>.npy``, so
+two builds can be compared output for output: the inputs are seeded, so the same arguments give the
+same inputs in every run.
+
+``--full`` adds everything else (untimed for `value`): the per-kernel probes and the roofline, the
+CPU baseline, the other configurations' and call sites' legs.  Among them ``call_site``: ms per view
+of train.py's whole render call
 site, (a) the reference's way -- torch activations + their autograd + the drop-in -- and (b) the
 fused ``rasterize_parameters`` path (activations inside the kernels).
 
@@ -19,8 +27,8 @@ N > 1: launched by torch.distributed.run, one process per GPU; the step's N * V 
 (step * N * V + k) mod 27 are sharded round-robin over ranks (splat_dp.shard_views; camera data
 parallelism, weak scaling: fixed views per GPU), then splat_dp.GradAllReduce sums the gradients.
 
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (HIP events inside libgsr on
-the stream the kernel runs on) and the CPU-oracle baseline (rank 0, N = 1 only).
+Prints ONE JSON line (rank 0); with ``--full`` it also holds the roofline of the dominant kernel (HIP
+events inside libgsr on the stream the kernel runs on) and the CPU-oracle baseline (rank 0, N = 1 only).
 """
 import argparse
 import json
@@ -526,6 +534,24 @@ def step_stats(views_per_step, P, ms):
                                         for q in (75, 50, 25)]}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs writes at most this much (the limit is 64 MB in all)
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: every tensor of ``arrays`` (name -> tensor) as ``dirpath/<name>.npy``, float32.
+    The arrays share DUMP_BUDGET_BYTES equally; one over its share is written as a sample of its
+    flattened elements at indices drawn from a generator seeded by the array's position, so the same
+    arguments sample the same elements in every run and every build."""
+    os.makedirs(dirpath, exist_ok=True)
+    cap = max(1, DUMP_BUDGET_BYTES // 4 // max(len(arrays), 1))
+    for i, (name, t) in enumerate(arrays.items()):
+        a = t.detach()
+        if a.numel() > cap:
+            idx = np.sort(np.random.default_rng(i).integers(0, a.numel(), size=cap))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(dirpath, name + ".npy"), a.to(torch.float32).cpu().numpy())
+
+
 def timed_steps(fn, steps, warmup, dev, host=None):
     """Run fn(it) warmup times, then `steps` times with an event on the current stream after each
     step: per-step device intervals (ms).  ``host``: a list that receives each step's host time (ms,
@@ -783,6 +809,16 @@ def main():
                          "node (this rank's share of it) before the GPU runtime starts -- a launcher's numactl; the "
                          "submitting threads otherwise wander over the shared host's 256 CPUs (0 = off; "
                          "splat_affinity.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the per-kernel probes and the roofline, the mean pair count, "
+                         "the CPU baseline and every call-site / configuration leg (the options below choose "
+                         "among them and have no effect without --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float32): the step's rendered images (summed step shape) and the gradients it "
+                         "left on the leaves; C5: the parameters of the rank's first and last frame after "
+                         "the step.  Arrays over their share of 48 MB are written as a fixed seeded sample; "
+                         "N > 1: every rank writes rank<r>_<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="OpenMP threads of the CPU baseline (0 = every CPU this process may run on, "
@@ -936,20 +972,21 @@ def main():
         # all-reduce + reset on the main stream is declared with grad_fence, so the next step's
         # forwards run during the all-reduce and only its first gradient write waits for it.
         # solo: one stream, one submitting thread (per-kernel times without concurrency); keep: leave
-        # the step's (reduced) gradients in place
-        rstep(views_of(it), solo=solo)
+        # the step's (reduced) gradients in place.  Returns the step's images (summed shape) or None
+        imgs = rstep(views_of(it), solo=solo)
         for s in streams:
             main_stream.wait_stream(s)  # the step ends on the main stream (its end event, the reduce)
         if reducer is not None:
             reducer.reduce()  # one flat-bucket all-reduce (SUM) of every gradient over RCCL
             if keep:
-                return
+                return imgs
             reducer.zero_()
             _C.grad_fence(*grads_of())
             leaves["means2D"].grad = None
         elif not keep:
             for p in leaves.values():
                 p.grad = None
+        return imgs
 
     fits = None
     if c5_cfg:
@@ -997,51 +1034,60 @@ def main():
 
     for it in range(args.warmup):
         step(it)
-    probe_steps = min(args.probe_steps, 1) if c5_cfg else args.probe_steps
-    # untimed probe: events around every kernel (they add launch gaps, so not in the timed region)
-    torch.cuda.synchronize()
-    _C.profile_reset()
-    _C.profile_select(None)
-    _C.profile_enable(True)
-    for it in range(probe_steps):
-        step(args.warmup + it)
-    torch.cuda.synchronize()
-    _C.profile_enable(False)
-    probe = {ph: _C.profile_read(ph) for ph in PHASES}
-    dom = max(PHASES, key=lambda ph: probe[ph][0])
-    # untimed solo probe (not C5): the same steps on one stream, one thread -- each kernel's time
-    # without the other streams' kernels sharing the CUs (the roofline's kernel alone)
-    solo = None
-    if fits is None and probe_steps > 0:
+    # --full only: the probes, and with them the dominant kernel whose events the timed region carries
+    probe_steps, probe, dom, solo = 0, None, None, None
+    if args.full:
+        probe_steps = min(args.probe_steps, 1) if c5_cfg else args.probe_steps
+        # untimed probe: events around every kernel (they add launch gaps, so not in the timed region)
         torch.cuda.synchronize()
         _C.profile_reset()
+        _C.profile_select(None)
         _C.profile_enable(True)
         for it in range(probe_steps):
-            step(args.warmup + it, solo=True)
+            step(args.warmup + it)
         torch.cuda.synchronize()
         _C.profile_enable(False)
-        solo = {ph: _C.profile_read(ph) for ph in PHASES}
-    # timed region: HIP events only around the dominant kernel (its roofline), host timers on, and an
-    # event on the main stream at every step end (the step ends there): per-step device intervals
+        probe = {ph: _C.profile_read(ph) for ph in PHASES}
+        dom = max(PHASES, key=lambda ph: probe[ph][0])
+        # untimed solo probe (not C5): the same steps on one stream, one thread -- each kernel's time
+        # without the other streams' kernels sharing the CUs (the roofline's kernel alone)
+        if fits is None and probe_steps > 0:
+            torch.cuda.synchronize()
+            _C.profile_reset()
+            _C.profile_enable(True)
+            for it in range(probe_steps):
+                step(args.warmup + it, solo=True)
+            torch.cuda.synchronize()
+            _C.profile_enable(False)
+            solo = {ph: _C.profile_read(ph) for ph in PHASES}
+    # timed region: an event on the main stream at every step end (the step ends there): per-step
+    # device intervals.  --full: also HIP events around the dominant kernel (its roofline) and the
+    # host timers.  --dump-outputs: the last step leaves its gradients in place
     first = args.warmup + probe_steps
     ends = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    _C.profile_reset()
-    _C.profile_select([dom])
-    _C.profile_enable(True)
+    if args.full:
+        _C.profile_reset()
+        _C.profile_select([dom])
+        _C.profile_enable(True)
+    last_images = None
     t0 = time.perf_counter()
     ends[0].record(main_stream)
     for it in range(args.steps):
-        step(first + it)
+        if args.dump_outputs is not None and it == args.steps - 1:
+            last_images = step(first + it, keep=True)
+        else:
+            step(first + it)
         ends[it + 1].record(main_stream)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    _C.profile_enable(False)
+    if args.full:
+        _C.profile_enable(False)
     step_ms = sorted(ends[i].elapsed_time(ends[i + 1]) for i in range(args.steps))
     median_ms = float(np.median(step_ms))
     if dist is not None:
@@ -1050,8 +1096,27 @@ def main():
         elapsed, median_ms = float(t[0].item()), float(t[1].item())
 
     # dominant kernel's device time inside the timed region (HIP events on its launch stream)
-    tot_ms, cnt = _C.profile_read(dom)
-    _C.profile_select(None)
+    tot_ms, cnt = _C.profile_read(dom) if args.full else (0.0, 0)
+    if args.full:
+        _C.profile_select(None)
+    if args.dump_outputs is not None:  # the last timed step's images and (reduced) gradients, or C5's fits
+        pre = f"rank{rank}_" if world > 1 else ""
+        arrays = {}
+        if fits is not None:
+            for t in sorted({fits.frames[0], fits.frames[-1]}):
+                arrays.update({f"{pre}frame{t}_{k}": v for k, v in fits.params[t].items()})
+        else:
+            arrays.update({f"{pre}image_{k}": img for k, img in enumerate(last_images or [])})
+            arrays.update({f"{pre}grad_{k}": v.grad for k, v in leaves.items() if v.grad is not None})
+        dump_outputs(args.dump_outputs, arrays)
+        last_images = arrays = None
+        if reducer is not None:  # what the step itself does after its reduce when it keeps nothing
+            reducer.zero_()
+            _C.grad_fence(*grads_of())
+            leaves["means2D"].grad = None
+        else:
+            for p in leaves.values():
+                p.grad = None
     checksum = None
     if args.grad_checksum and fits is None:  # one more step, its (reduced) gradients kept and saved
         it = first + args.steps
@@ -1066,6 +1131,64 @@ def main():
         for p in leaves.values():
             if reducer is None or p is leaves["means2D"]:
                 p.grad = None
+    ms_per_step = elapsed / args.steps * 1e3
+    # value: the median step (SURVEY.md 8(d): median of >= 20 reps) -- per-step device intervals
+    # between the step-end events on the main stream; the mean over the timed region beside it
+    value = views_per_step * cfg.P / (median_ms * 1e-3) / 1e6
+    value_mean = views_per_step * cfg.P / (elapsed / args.steps) / 1e6
+
+    def result_line():
+        """The headline's keys: all of a plain run's line, the head of a --full run's."""
+        workload = {
+            "C2": f"C2: {cfg.P} Gaussians, RGB, {cfg.width}x{cfg.height}, the 4 cameras (yaw 0/90/180/270) "
+                  f"per GPU per step, fwd+bwd" + (", RCCL SUM all-reduce of the gradients" if world > 1 else ""),
+            "C3": f"C3: {cfg.P} Gaussians, SH{cfg.sh_degree}, {cfg.width}x{cfg.height}, 27-camera rig, "
+                  f"{V} view(s)/GPU/step, fwd+bwd" + (", RCCL SUM all-reduce of the gradients" if world > 1 else ""),
+            "C3M": f"C3M: C3 with half of the {cfg.P} means in 16 tight clusters (densified-scene stand-in), "
+                   f"SH{cfg.sh_degree}, {cfg.width}x{cfg.height}, {V} view(s)/GPU/step, fwd+bwd",
+            "C4": f"C4: {cfg.P} Gaussians, RGB, {cfg.width}x{cfg.height}, the 27-camera rig per step sharded "
+                  f"round-robin over {world} GPU(s), fwd+bwd" + (", one RCCL SUM all-reduce" if world > 1 else ""),
+            "C5": f"C5: {cfg.P} Gaussians x 150 frames, RGB, {cfg.width}x{cfg.height}, independent per-frame "
+                  f"fits (own parameters + Adam state per frame), frames sharded in blocks over {world} GPU(s); "
+                  f"one step = one optimisation iteration of every frame ({V} rig views fwd + fused L1/SSIM "
+                  f"+ bwd + fused Adam); no collective",
+        }[args.config]
+        shape = ("view losses summed, one backward (deferred multi-view per-Gaussian pass)"
+                 if args.step_shape == "summed" else "one backward per view")
+        return {
+            "metric": "Msplats/sec fwd+bwd @1080p (1M gauss)" if args.config in ("C3", "C3M", "C4") else
+                      "Msplats/sec fwd+bwd @800x800 (100k gauss, 4 cameras)" if args.config == "C2" else
+                      "Msplats/sec fwd+bwd @1080p (2M gauss per-frame fits)",
+            "value": round(value, 3), "unit": "Msplats/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "strong" if args.config in ("C4", "C5") else "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic", "full": args.full,
+            "value_definition": "views x Gaussians / median step (device intervals between the step-end "
+                                "events on the main stream; max over ranks)",
+            "median_ms_per_step": round(median_ms, 4), "value_mean": round(value_mean, 3),
+            "step_ms_quartiles": [round(float(np.percentile(step_ms, q)), 4) for q in (25, 50, 75)],
+            "config": {"workload": workload, "gaussians": cfg.P, "views_per_step": views_per_step,
+                       "views_per_gpu": [len(splat_dp.shard_views(list(range(views_per_step)), r, world))
+                                         for r in range(world)],
+                       "image": f"{cfg.width}x{cfg.height}", "sh_degree": cfg.sh_degree,
+                       "parallelism": f"frame-dp{world}" if c5_cfg else f"camera-dp{world}",
+                       "streams_per_gpu": len(streams),
+                       "step_shape": "per frame: view losses summed, one backward, one Adam step" if c5_cfg else shape,
+                       "submission": "one host thread per stream" if rstep.pool is not None else "one host thread",
+                       "means2D": None if c5_cfg else ("one fresh zero leaf per render (shared.py:38-41)"
+                                                       if args.means2d == "per-view" else "one leaf shared by the step's views"),
+                       "backend": args.backend if dist is not None else None,
+                       "host_cpus": pinned or "unpinned"},
+            "dump_outputs": args.dump_outputs, "grad_checksum": checksum,
+        }
+
+    if not args.full:  # a plain run ends here
+        if rank == 0:
+            print(json.dumps(result_line()), flush=True)
+        rstep.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     legs = world == 1 and args.config == "C3"
     call_site = None
     if legs and args.call_site_steps > 0:
@@ -1160,11 +1283,6 @@ def main():
     # reported beside it, labelled as such
     kernel_ms = solo_ms if solo_ms else avg_ms
     achieved = bytes_launch / (kernel_ms * 1e-3) / 1e9
-    ms_per_step = elapsed / args.steps * 1e3
-    # value: the median step (SURVEY.md 8(d): median of >= 20 reps) -- per-step device intervals
-    # between the step-end events on the main stream; the mean over the timed region beside it
-    value = views_per_step * cfg.P / (median_ms * 1e-3) / 1e6
-    value_mean = views_per_step * cfg.P / (elapsed / args.steps) / 1e6
     pipe_b = pipeline_bytes(cfg.P, K, N, T, F, SH)
     pipe_gbps = pipe_b * views_per_step / world / (median_ms * 1e-3) / 1e9
     if rank == 0:
@@ -1179,47 +1297,9 @@ def main():
             cpu = cpu_baseline_oracle(cfg, params_cpu, cam_cpu, dl.cpu(), args.cpu_threads)
             if pinned:
                 splat_affinity.unpin_host_threads(pinned)
-        workload = {
-            "C2": f"C2: {cfg.P} Gaussians, RGB, {cfg.width}x{cfg.height}, the 4 cameras (yaw 0/90/180/270) "
-                  f"per GPU per step, fwd+bwd" + (", RCCL SUM all-reduce of the gradients" if world > 1 else ""),
-            "C3": f"C3: {cfg.P} Gaussians, SH{cfg.sh_degree}, {cfg.width}x{cfg.height}, 27-camera rig, "
-                  f"{V} view(s)/GPU/step, fwd+bwd" + (", RCCL SUM all-reduce of the gradients" if world > 1 else ""),
-            "C3M": f"C3M: C3 with half of the {cfg.P} means in 16 tight clusters (densified-scene stand-in), "
-                   f"SH{cfg.sh_degree}, {cfg.width}x{cfg.height}, {V} view(s)/GPU/step, fwd+bwd",
-            "C4": f"C4: {cfg.P} Gaussians, RGB, {cfg.width}x{cfg.height}, the 27-camera rig per step sharded "
-                  f"round-robin over {world} GPU(s), fwd+bwd" + (", one RCCL SUM all-reduce" if world > 1 else ""),
-            "C5": f"C5: {cfg.P} Gaussians x 150 frames, RGB, {cfg.width}x{cfg.height}, independent per-frame "
-                  f"fits (own parameters + Adam state per frame), frames sharded in blocks over {world} GPU(s); "
-                  f"one step = one optimisation iteration of every frame ({V} rig views fwd + fused L1/SSIM "
-                  f"+ bwd + fused Adam); no collective",
-        }[args.config]
-        shape = ("view losses summed, one backward (deferred multi-view per-Gaussian pass)"
-                 if args.step_shape == "summed" else "one backward per view")
-        out = {
-            "metric": "Msplats/sec fwd+bwd @1080p (1M gauss)" if args.config in ("C3", "C3M", "C4") else
-                      "Msplats/sec fwd+bwd @800x800 (100k gauss, 4 cameras)" if args.config == "C2" else
-                      "Msplats/sec fwd+bwd @1080p (2M gauss per-frame fits)",
-            "value": round(value, 3), "unit": "Msplats/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "strong" if args.config in ("C4", "C5") else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "value_definition": "views x Gaussians / median step (device intervals between the step-end "
-                                "events on the main stream; max over ranks)",
-            "median_ms_per_step": round(median_ms, 4), "value_mean": round(value_mean, 3),
-            "step_ms_quartiles": [round(float(np.percentile(step_ms, q)), 4) for q in (25, 50, 75)],
-            "config": {"workload": workload, "gaussians": cfg.P, "views_per_step": views_per_step,
-                       "views_per_gpu": [len(splat_dp.shard_views(list(range(views_per_step)), r, world))
-                                         for r in range(world)],
-                       "image": f"{cfg.width}x{cfg.height}", "sh_degree": cfg.sh_degree,
-                       "mean_num_rendered": int(K), "max_tile_pairs": max_tile,
-                       "parallelism": f"frame-dp{world}" if c5_cfg else f"camera-dp{world}",
-                       "streams_per_gpu": len(streams),
-                       "step_shape": "per frame: view losses summed, one backward, one Adam step" if c5_cfg else shape,
-                       "submission": "one host thread per stream" if rstep.pool is not None else "one host thread",
-                       "means2D": None if c5_cfg else ("one fresh zero leaf per render (shared.py:38-41)"
-                                                       if args.means2d == "per-view" else "one leaf shared by the step's views"),
-                       "backend": args.backend if dist is not None else None,
-                       "host_cpus": pinned or "unpinned"},
+        out = result_line()
+        out["config"].update({"mean_num_rendered": int(K), "max_tile_pairs": max_tile})
+        out.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2),
                          "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
@@ -1261,8 +1341,7 @@ def main():
             "loss_call_site": loss_site,
             "densify_call_site": dens_site,
             "io_call_site": io_site,
-            "grad_checksum": checksum,
-        }
+        })
         print(json.dumps(out), flush=True)
     rstep.close()
     if dist is not None:

@@ -7,7 +7,7 @@ for rep in ${REPS:-1 2 3}; do
   k=0
   for e in "$@"; do
     k=$((k + 1))
-    env $e timeout -k 10 200 python -u bench.py --steps ${STEPS:-200} ${BENCH_ARGS:-} \
+    env $e timeout -k 10 200 python -u bench.py --full --steps ${STEPS:-200} ${BENCH_ARGS:-} \
       --call-site-steps 0 --train-steps ${TRAIN_STEPS:-0} --loss-steps 0 --densify-steps 0 --io-timesteps 0 --no-cpu-baseline \
       > gpurun_out/abenv/v$k.$rep.json 2> gpurun_out/abenv/v$k.$rep.err || { echo "$e failed"; tail -5 gpurun_out/abenv/v$k.$rep.err; exit 1; }
     python -c "

@@ -4,7 +4,7 @@ set -o pipefail
 mkdir -p gpurun_out/abs1
 for rep in 1 2; do
   for v in "$@"; do
-    GSR_LIB=$(pwd)/tools/ab/libgsr_$v.so timeout -k 10 200 python -u bench.py --streams 1 --steps 20 --call-site-steps 0 --loss-steps 0 --densify-steps 0 --io-timesteps 0 \
+    GSR_LIB=$(pwd)/tools/ab/libgsr_$v.so timeout -k 10 200 python -u bench.py --full --streams 1 --steps 20 --call-site-steps 0 --loss-steps 0 --densify-steps 0 --io-timesteps 0 \
       --no-cpu-baseline ${BENCH_ARGS:-} > gpurun_out/abs1/$v.$rep.json 2> gpurun_out/abs1/$v.$rep.err || { echo "$v failed"; tail -5 gpurun_out/abs1/$v.$rep.err; exit 1; }
     python -c "
 import json; d=json.loads([l for l in open('gpurun_out/abs1/$v.$rep.json') if l.startswith('{')][0])

@@ -2,7 +2,7 @@
 set -u
 O=$1; N=$2; shift 2; mkdir -p "$O"
 LEGS="--steps 1 --warmup 1 --probe-steps 0 --call-site-steps 0 --train-steps 0 --loss-steps 0 --densify-steps 0 --io-timesteps 0 --unchanged-steps 0 --no-cpu-baseline"
-EXTRA_DEF="--inference-steps 0"
+EXTRA_DEF="--inference-steps 0 --full"
 for r in $(seq "$N"); do
   for v in "$@"; do
     case "$v" in

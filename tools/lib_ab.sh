@@ -10,11 +10,11 @@ LEGS="--call-site-steps 0 --train-steps 0 --loss-steps 0 --densify-steps 0 --io-
 for r in $(seq "$N"); do
   for v in "$@"; do
     case "$v" in
-      def) GSR_LIB=animating-gaussian-splats_amd/diff_gaussian_rasterization/libgsr.so timeout -k 10 300 python -u bench.py $LEGS --inference-steps 0 > "$O/lab_$v$r.json" 2> "$O/lab_$v$r.err" ;;
-      *_fast) GSR_EXACT_THRESHOLDS=0 GSR_LIB=tools/ab/libgsr_${v%_fast}.so timeout -k 10 300 python -u bench.py $LEGS --inference-steps 0 > "$O/lab_$v$r.json" 2> "$O/lab_$v$r.err" ;;
-      fast) GSR_EXACT_THRESHOLDS=0 timeout -k 10 300 python -u bench.py $LEGS --inference-steps 0 > "$O/lab_$v$r.json" 2> "$O/lab_$v$r.err" ;;
+      def) GSR_LIB=animating-gaussian-splats_amd/diff_gaussian_rasterization/libgsr.so timeout -k 10 300 python -u bench.py --full $LEGS --inference-steps 0 > "$O/lab_$v$r.json" 2> "$O/lab_$v$r.err" ;;
+      *_fast) GSR_EXACT_THRESHOLDS=0 GSR_LIB=tools/ab/libgsr_${v%_fast}.so timeout -k 10 300 python -u bench.py --full $LEGS --inference-steps 0 > "$O/lab_$v$r.json" 2> "$O/lab_$v$r.err" ;;
+      fast) GSR_EXACT_THRESHOLDS=0 timeout -k 10 300 python -u bench.py --full $LEGS --inference-steps 0 > "$O/lab_$v$r.json" 2> "$O/lab_$v$r.err" ;;
       *tree) timeout -k 10 300 python -u tools/ab/$v/bench.py $LEGS > "$O/lab_$v$r.json" 2> "$O/lab_$v$r.err" ;;
-      *) GSR_LIB=tools/ab/libgsr_$v.so timeout -k 10 300 python -u bench.py $LEGS --inference-steps 0 > "$O/lab_$v$r.json" 2> "$O/lab_$v$r.err" ;;
+      *) GSR_LIB=tools/ab/libgsr_$v.so timeout -k 10 300 python -u bench.py --full $LEGS --inference-steps 0 > "$O/lab_$v$r.json" 2> "$O/lab_$v$r.err" ;;
     esac || { echo "bench $v failed"; tail -5 "$O/lab_$v$r.err"; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$O/lab_$v$r.json').read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ else
   CTRS="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_INST_ANY SQ_WAIT_ANY"
 fi
 R=$(pwd); mkdir -p "$O/pmc_${v}_$set_"; OO=$(cd "$O/pmc_${v}_$set_" && pwd)
-B=$R/bench.py; EXTRA="--inference-steps 0"
+B=$R/bench.py; EXTRA="--inference-steps 0 --full"
 case "$v" in
   def) export GSR_LIB=$R/animating-gaussian-splats_amd/diff_gaussian_rasterization/libgsr.so ;;
   *tree) B=$R/tools/ab/$v/bench.py; EXTRA="" ;;

@@ -4,7 +4,7 @@
 set -u
 O=$1; N=$2; shift 2
 mkdir -p "$O"
-LEGS="--steps 1 --warmup 1 --probe-steps 0 --call-site-steps 0 --inference-steps 0 --train-steps 0 --loss-steps 0 --densify-steps 0 --io-timesteps 0 --c2-steps 0 --no-cpu-baseline --unchanged-steps 60"
+LEGS="--full --steps 1 --warmup 1 --probe-steps 0 --call-site-steps 0 --inference-steps 0 --train-steps 0 --loss-steps 0 --densify-steps 0 --io-timesteps 0 --c2-steps 0 --no-cpu-baseline --unchanged-steps 60"
 for r in $(seq "$N"); do
   for v in "$@"; do
     GSR_LIB=tools/ab/libgsr_$v.so timeout -k 10 300 python -u bench.py $LEGS > "$O/u_$v$r.json" 2> "$O/u_$v$r.err" \
