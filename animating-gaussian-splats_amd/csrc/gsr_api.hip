@@ -1203,6 +1203,88 @@ int gsr_l1_ssim_backward(int planes, int H, int W, const float *img1, const floa
     return GSR_OK;
 }
 
+// ---- rigidity loss + k-nearest neighbours ---------------------------------------------------
+}  // extern "C"
+namespace {
+constexpr int kKnnMaxK = 32;
+struct RigidScratch {
+    size_t partial, save_m, save_q, save_u, total;
+    RigidScratch(int F, int k, bool save) {
+        const size_t f = (size_t)F;
+        partial = 0;
+        size_t o = align256(sizeof(double) * (size_t)rigid_blocks(F));
+        save_m = o; if (save) o = align256(o + sizeof(float) * 3 * f);
+        save_q = o; if (save) o = align256(o + sizeof(float) * 4 * f);
+        save_u = o; if (save) o = align256(o + sizeof(float) * 3 * f * (size_t)k);
+        total = o;
+    }
+};
+int check_rigid(int P, int F, int k) {
+    if (P < 0 || F < 0 || k < 0) return fail(GSR_ERR_ARG, "rigidity: negative size");
+    if (F > P) return fail(GSR_ERR_ARG, "rigidity: %d foreground rows of %d Gaussians", F, P);
+    if ((size_t)F * (size_t)k >= (size_t)1 << 31) return fail(GSR_ERR_UNSUPPORTED, "rigidity: more than 2^31 edges");
+    return GSR_OK;
+}
+}  // namespace
+extern "C" {
+
+int gsr_knn(int n, const float *points, int k, int *out_indices, double *out_sq_distances, void *stream) {
+    if (n < 0 || k < 1) return fail(GSR_ERR_ARG, "knn: n must be >= 0 and k >= 1 (got n = %d, k = %d)", n, k);
+    if (k > kKnnMaxK) return fail(GSR_ERR_UNSUPPORTED, "knn: k = %d (at most %d supported)", k, kKnnMaxK);
+    if (n <= k) return fail(GSR_ERR_ARG, "knn: %d points have no %d other points each", n, k);
+    if ((size_t)n * (size_t)k >= (size_t)1 << 31) return fail(GSR_ERR_UNSUPPORTED, "knn: more than 2^31 results");
+    if (!points || !out_indices || !out_sq_distances) return fail(GSR_ERR_ARG, "knn: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "knn");
+    HIP_TRY(launch_knn(n, points, k, out_indices, out_sq_distances, s));
+    return GSR_OK;
+}
+
+size_t gsr_rigidity_scratch_bytes(int F, int k, int save_for_backward) {
+    return RigidScratch(F < 0 ? 0 : F, k < 0 ? 0 : k, save_for_backward != 0).total;
+}
+
+int gsr_rigidity_forward(int P, int F, int k, const float *means, const float *rotation_quaternions,
+                         const int *foreground_rows, const int *neighbor_rows, const float *weights,
+                         const float *previous_offsets, const float *previous_inverted_rotations, void *scratch,
+                         int save_for_backward, float *out_loss, void *stream) {
+    int rc = check_rigid(P, F, k);
+    if (rc) return rc;
+    if (F == 0 || k == 0) return fail(GSR_ERR_ARG, "rigidity: no foreground edges (the mean is undefined)");
+    if (!means || !rotation_quaternions || !foreground_rows || !neighbor_rows || !weights || !previous_offsets ||
+        !previous_inverted_rotations || !scratch || !out_loss)
+        return fail(GSR_ERR_ARG, "rigidity: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const RigidScratch L(F, k, save_for_backward != 0);
+    char *base = (char *)scratch;
+    const bool sv = save_for_backward != 0;
+    Phase ph(s, "rigidity_fwd");
+    HIP_TRY(launch_rigid_fwd(F, k, means, rotation_quaternions, foreground_rows, neighbor_rows, weights,
+                             previous_offsets, previous_inverted_rotations, (double *)(base + L.partial),
+                             sv ? (float *)(base + L.save_u) : nullptr, sv ? (float *)(base + L.save_m) : nullptr,
+                             sv ? (float *)(base + L.save_q) : nullptr, out_loss, s));
+    return GSR_OK;
+}
+
+int gsr_rigidity_backward(int P, int F, int k, const int *row_to_foreground, const int *reverse_offsets,
+                          const int *reverse_edges, const void *scratch, const float *dL_dloss, float *dL_dmeans,
+                          float *dL_drotation_quaternions, void *stream) {
+    int rc = check_rigid(P, F, k);
+    if (rc) return rc;
+    if (P == 0 || (!dL_dmeans && !dL_drotation_quaternions)) return GSR_OK;
+    if (F == 0 || k == 0) return fail(GSR_ERR_ARG, "rigidity: no foreground edges");
+    if (!row_to_foreground || !reverse_offsets || !reverse_edges || !scratch || !dL_dloss)
+        return fail(GSR_ERR_ARG, "rigidity: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const RigidScratch L(F, k, true);
+    const char *base = (const char *)scratch;
+    Phase ph(s, "rigidity_bwd");
+    HIP_TRY(launch_rigid_bwd(P, F, k, row_to_foreground, reverse_offsets, reverse_edges,
+                             (const float *)(base + L.save_u), (const float *)(base + L.save_m),
+                             (const float *)(base + L.save_q), dL_dloss, dL_dmeans, dL_drotation_quaternions, s));
+    return GSR_OK;
+}
+
 // ---- densification --------------------------------------------------------------------------
 }  // extern "C"
 namespace {

@@ -124,6 +124,17 @@ hipError_t launch_ssim_bwd(int planes, int H, int W, const float *img1, const fl
                            const float *maps, const float *g_l1, const float *g_ssim, float *dimg1,
                            hipStream_t s);
 
+// rigidity loss + exact k-nearest neighbours (gsr_rigidity.hip)
+hipError_t launch_knn(int n, const float *pts, int k, int *out_idx, double *out_d2, hipStream_t s);
+int rigid_blocks(int F);
+hipError_t launch_rigid_fwd(int F, int k, const float *means, const float *quats, const int *fg_rows,
+                            const int *nbr_rows, const float *weights, const float *prev_off, const float *prev_inv,
+                            double *partial, float *save_u, float *save_m, float *save_q, float *out_loss,
+                            hipStream_t s);
+hipError_t launch_rigid_bwd(int P, int F, int k, const int *row_to_fg, const int *rev_off, const int *rev_edge,
+                            const float *save_u, const float *save_m, const float *save_q, const float *g_loss,
+                            float *dmeans, float *dquats, hipStream_t s);
+
 // densification (gsr_densify.hip)
 struct DensArgs {
     int P, prune_big;

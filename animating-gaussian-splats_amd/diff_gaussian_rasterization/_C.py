@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "gsr_forward_info_call", "gsr_spec_stats", "gsr_sums_bytes", "gsr_prealloc_alloc", "gsr_spec_binning_bytes",
     "gsr_forward_async", "gsr_forward_resolve", "gsr_forward_release", "gsr_forward_query", "gsr_async_stats",
     "gsr_spec_keys", "gsr_async_shutdown", "gsr_debug_async_fault", "gsr_set_exact_thresholds",
+    "gsr_knn", "gsr_rigidity_scratch_bytes", "gsr_rigidity_forward", "gsr_rigidity_backward",
 )
 
 
@@ -180,6 +181,14 @@ def load_library():
     L.gsr_spec_binning_bytes.argtypes = [i, i, i, i]
     L.gsr_set_exact_thresholds.restype = i
     L.gsr_set_exact_thresholds.argtypes = [i]
+    L.gsr_knn.restype = i
+    L.gsr_knn.argtypes = [i, vp, i, vp, vp, vp]
+    L.gsr_rigidity_scratch_bytes.restype = ctypes.c_size_t
+    L.gsr_rigidity_scratch_bytes.argtypes = [i, i, i]
+    L.gsr_rigidity_forward.restype = i
+    L.gsr_rigidity_forward.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, vp]
+    L.gsr_rigidity_backward.restype = i
+    L.gsr_rigidity_backward.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
     if L.gsr_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libgsr.so ABI {L.gsr_abi_version()} != binding ABI {ABI_VERSION}: rebuild it")
     global _PREALLOC_FN

@@ -15,6 +15,9 @@ densify_gaussians                           :239-245    splat_densify.densify_ga
 optimizer.step(); zero_grad(set_to_none)    :246-247    splat_adam.FusedAdam (one launch)
 =====================================================  ============================================
 
+``train_step_loss`` is the loss of one train.py step (train.py:395-418): the views' renders and image
+losses as above plus the rigidity term of ``splat_rigidity``, evaluated once per step.
+
 ``View`` restates shared.py:13-18.  The image-render ``means2D`` is a leaf that receives the same
 screen-space (NDC) gradient the reference reads through ``retain_grad`` (densify.py:119).
 """
@@ -26,9 +29,10 @@ import torch
 
 import splat_densify
 import splat_loss
+import splat_rigidity
 from diff_gaussian_rasterization import GaussianRasterizationSettings, rasterize_parameters
 
-__all__ = ["View", "densify_iteration", "create_densification_variables"]
+__all__ = ["View", "densify_iteration", "create_densification_variables", "train_step_loss"]
 
 
 @dataclass
@@ -70,3 +74,22 @@ def densify_iteration(params, view, densification_variables, optimizer, scene_ra
         optimizer.step()
         optimizer.zero_grad(set_to_none=True)
     return (total.detach(), image_loss.detach(), segmentation_loss.detach()), info
+
+
+def train_step_loss(params, views, neighbor_info, foreground_info):
+    """train.py:395-418 ``calculate_loss`` without the logging: every view rendered
+    (``rasterize_parameters``) and compared (fused L1 + SSIM), plus the rigidity term.  The reference
+    evaluates the rigidity term once per view although it does not depend on the view; here it is
+    evaluated once and multiplied by ``V = len(views)``.  Returns ``(0.8 sum l1 + 0.2 sum (1 - ssim) +
+    3 V rigidity, sum l1, sum (1 - ssim), V rigidity)``; call ``backward()`` on the first."""
+    if not views:
+        raise ValueError("train_step_loss: no views")
+    l1_sum = ssim_sum = None
+    for view in views:
+        image, _, _ = rasterize_parameters(params, view.render_settings)
+        l1, ssim_loss = splat_loss.l1_and_ssim_loss(image, view.image)
+        l1_sum = l1 if l1_sum is None else l1_sum + l1
+        ssim_sum = ssim_loss if ssim_sum is None else ssim_sum + ssim_loss
+    rigidity_sum = len(views) * splat_rigidity.calculate_rigidity_loss(params, neighbor_info, foreground_info)
+    total = 0.8 * l1_sum + 0.2 * ssim_sum + 3 * rigidity_sum
+    return total, l1_sum, ssim_sum, rigidity_sum

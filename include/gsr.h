@@ -371,6 +371,36 @@ int gsr_l1_ssim_backward(int planes, int height, int width, const float *img1, c
                          const void *scratch, const float *dL_dl1, const float *dL_dssim,
                          float *dL_dimg1, void *stream);
 
+/* ---- Rigidity loss and exact k-nearest neighbours (additive to ABI 21) ------------------------
+ * gsr_knn: the k nearest OTHER points of each of n fp32 points (n, 3), the counterpart of
+ * compute_knn_indices_and_squared_distances (shared.py:45-61).  Squared distances are evaluated in
+ * float64 from the fp32 coordinates; out_indices / out_sq_distances are (n, k) row-major, ascending in
+ * distance.  A point is excluded from its own list by its index (not as "the first result"), and equal
+ * distances are ordered by the lower index, so the result is defined for coincident points as well.
+ * Exact brute force, split over launches of bounded length.  1 <= k <= 32 < n. */
+int gsr_knn(int n, const float *points, int k, int *out_indices, double *out_sq_distances, void *stream);
+/* calculate_rigidity_loss (train.py:325-351) over F foreground Gaussians with k neighbours each, of P
+ * Gaussians in all.  means (P, 3) and rotation_quaternions (P, 4, raw: normalised inside) are the full
+ * parameter arrays; foreground_rows (F) gives the row of foreground Gaussian i.  The neighbour arrays
+ * are neighbour-major: neighbor_rows (k, F) the ROW (in [0, P)) of i's j-th neighbour, weights (k, F),
+ * previous_offsets (k, 3, F); previous_inverted_rotations is (F, 4).  The caller guarantees the index
+ * ranges.  out_loss: device float scalar, the mean over the F k terms.  With save_for_backward the
+ * scratch buffer (gsr_rigidity_scratch_bytes with the same flag) also receives the derivatives the
+ * backward gathers and must be kept alive until then. */
+size_t gsr_rigidity_scratch_bytes(int F, int k, int save_for_backward);
+int gsr_rigidity_forward(int P, int F, int k, const float *means, const float *rotation_quaternions,
+                         const int *foreground_rows, const int *neighbor_rows, const float *weights,
+                         const float *previous_offsets, const float *previous_inverted_rotations, void *scratch,
+                         int save_for_backward, float *out_loss, void *stream);
+/* dL_dmeans (P, 3) / dL_drotation_quaternions (P, 4) (either may be NULL = not wanted) are written in
+ * full, background rows with zeros.  row_to_foreground (P): foreground index of a row or -1;
+ * reverse_offsets (F + 1) / reverse_edges (F k): CSR over "which edges j * F + i list Gaussian m", whose
+ * stored order is the summation order (no atomics: two runs are bitwise equal).  dL_dloss is a DEVICE
+ * scalar (no host synchronisation). */
+int gsr_rigidity_backward(int P, int F, int k, const int *row_to_foreground, const int *reverse_offsets,
+                          const int *reverse_edges, const void *scratch, const float *dL_dloss, float *dL_dmeans,
+                          float *dL_drotation_quaternions, void *stream);
+
 /* ---- Densification: statistics, clone / split / prune with Adam state surgery (ABI >= 4) ------
  * SURVEY.md 8(f) row 2.  Replaces update_max_2d_radii_and_visibility_mask (densify.py:154-162),
  * accumulate_mean_2d_gradients (external.py:113-124) and the body of densify_gaussians
@@ -462,7 +492,7 @@ int gsr_views_pack(int frames, int H, int W, const uint8_t *rgb, const uint8_t *
 
 /* Per-phase device timing with HIP events recorded on the call's stream (off by default).
  * Phases: "preprocess", "bin_count", "bin_scan", "bin_emit", "tile_sort", "render_fwd",
- * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack".  gsr_profile_read synchronises on the recorded events. */
+ * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "knn", "rigidity_fwd", "rigidity_bwd".  gsr_profile_read synchronises on the recorded events. */
 int gsr_profile_enable(int on);
 /* Restrict event recording to a comma-separated list of phases (NULL or "" = every phase), so a
  * timed region can carry the events of one kernel only.  Host-side timers are unaffected. */
