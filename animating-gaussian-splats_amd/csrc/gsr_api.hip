@@ -1,4 +1,5 @@
-// gsr_api.hip -- C ABI of libgsr (declared in include/gsr.h).
+// gsr_api.hip -- C ABI of libgsr (declared in include/gsr.h): the rasterizer's forward and backward,
+// the error string and the profiling calls.  The other entry points are in gsr_api_aux.hip.
 //
 // Host-side orchestration of the forward/backward kernel pipelines: argument validation with the
 // reference's error behaviour, workspace carving, the single num_rendered read-back per forward,
@@ -18,7 +19,6 @@
 #include <map>
 #include <memory>
 #include <unordered_map>
-#include <atomic>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -26,6 +26,7 @@
 #include "../../include/gsr.h"
 #include "gsr_common.h"
 #include "gsr_internal.h"
+#include "gsr_host.h"
 
 using namespace gsr;
 
@@ -33,23 +34,6 @@ using namespace gsr;
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess) return fail(GSR_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
 
 // ---- per-phase event profiling ----
 struct ProfRec { std::string phase; hipEvent_t a, b; };
@@ -70,22 +54,43 @@ hipEvent_t ev_get() {
     return e;
 }
 
-struct Phase {
-    hipStream_t s; const char *name; hipEvent_t a = nullptr, b = nullptr;
-    Phase(hipStream_t s_, const char *n) : s(s_), name(n) {
-        if (!g_prof_on) return;
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        if (!g_prof_sel.empty() && g_prof_sel.find("," + std::string(n) + ",") == std::string::npos) return;
-        a = ev_get(); b = ev_get();
-        if (a) (void)hipEventRecord(a, s);
-    }
-    ~Phase() {
-        if (!a || !b) return;
-        (void)hipEventRecord(b, s);
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        g_prof.push_back({name, a, b});
-    }
-};
+}  // namespace
+
+// ---- gsr_host.h: one definition for every translation unit of the C ABI ----
+int gsr::fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+gsr::Phase::Phase(hipStream_t s_, const char *n, bool on) : s(s_), name(n) {
+    if (!on || !g_prof_on) return;
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    if (!g_prof_sel.empty() && g_prof_sel.find("," + std::string(n) + ",") == std::string::npos) return;
+    a = ev_get(); b = ev_get();
+    if (a) (void)hipEventRecord(a, s);
+}
+gsr::Phase::~Phase() {
+    if (!a || !b) return;
+    (void)hipEventRecord(b, s);
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_prof.push_back({name, a, b});
+}
+
+gsr::HostPhase::HostPhase(const char *n) : name(n), t0(hclock::now()), on(g_prof_on) {}
+gsr::HostPhase::~HostPhase() {
+    if (!on) return;
+    const double ms = std::chrono::duration<double, std::milli>(hclock::now() - t0).count();
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_host_ms[name] += ms;
+    g_host_n[name] += 1;
+}
+
+namespace {
 
 // Cross-stream order of the gradient writes.  A caller may render its views on several HIP streams
 // (bench.py --streams, splat_train) so one view's memory-bound k_gauss_bwd overlaps another view's
@@ -160,20 +165,6 @@ HostWord pinned_word() {
 
 constexpr uint32_t kNoValue = 0xFFFFFFFFu;
 
-// host-side timers (profiling mode only)
-using hclock = std::chrono::steady_clock;
-struct HostPhase {
-    const char *name; hclock::time_point t0; bool on;
-    explicit HostPhase(const char *n) : name(n), t0(hclock::now()), on(g_prof_on) {}
-    ~HostPhase() {
-        if (!on) return;
-        const double ms = std::chrono::duration<double, std::milli>(hclock::now() - t0).count();
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        g_host_ms[name] += ms;
-        g_host_n[name] += 1;
-    }
-};
-
 int check_common(const gsr_camera *cam, const gsr_gaussians *g, bool need_opacity) {
     if (!cam || !g) return fail(GSR_ERR_ARG, "null camera or gaussians");
     if (g->P < 0) return fail(GSR_ERR_ARG, "P must be >= 0");
@@ -205,54 +196,109 @@ std::atomic<int> g_exact{[] {
     return (e && e[0] == '0') ? 0 : 1;
 }()};
 
-void fill_common(FwdArgs &a, const gsr_camera *cam, const gsr_gaussians *g) {
-    memset(&a, 0, sizeof(a));
-    a.exact = g_exact.load(std::memory_order_relaxed);
-    a.P = g->P; a.D = g->sh_degree; a.M = g->shs ? g->sh_coeffs : 0;
-    a.W = cam->image_width; a.H = cam->image_height;
-    a.gx = div_up(a.W, kTileW); a.gy = div_up(a.H, kTileH);
-    a.scale_modifier = g->scale_modifier;
-    a.act = g->activations;
-    a.tan_fovx = cam->tan_fovx; a.tan_fovy = cam->tan_fovy;
-    a.focal_y = a.H / (2.0f * a.tan_fovy);
-    a.focal_x = a.W / (2.0f * a.tan_fovx);
-    a.means3D = g->means3D; a.scales = g->scales; a.rotations = g->rotations; a.opacities = g->opacities;
-    a.shs = g->shs; a.colors_precomp = g->colors_precomp; a.cov3D_precomp = g->cov3D_precomp;
-    a.viewmatrix = cam->viewmatrix; a.projmatrix = cam->projmatrix; a.campos = cam->campos; a.bg = cam->bg;
+void fill_common(ViewIn &v, const gsr_camera *cam, const gsr_gaussians *g) {
+    memset(&v, 0, sizeof(v));
+    v.P = g->P; v.D = g->sh_degree; v.M = g->shs ? g->sh_coeffs : 0;
+    v.W = cam->image_width; v.H = cam->image_height;
+    v.gx = div_up(v.W, kTileW); v.gy = div_up(v.H, kTileH);
+    v.scale_modifier = g->scale_modifier;
+    v.act = g->activations;
+    v.tan_fovx = cam->tan_fovx; v.tan_fovy = cam->tan_fovy;
+    v.focal_y = v.H / (2.0f * v.tan_fovy);
+    v.focal_x = v.W / (2.0f * v.tan_fovx);
+    v.means3D = g->means3D; v.scales = g->scales; v.rotations = g->rotations; v.opacities = g->opacities;
+    v.shs = g->shs; v.colors_precomp = g->colors_precomp; v.cov3D_precomp = g->cov3D_precomp;
+    v.viewmatrix = cam->viewmatrix; v.projmatrix = cam->projmatrix; v.campos = cam->campos; v.bg = cam->bg;
     const bool vz = !cam->viewmatrix_stride[0] && !cam->viewmatrix_stride[1];
     const bool pz = !cam->projmatrix_stride[0] && !cam->projmatrix_stride[1];
-    a.cs.v0 = vz ? 4 : cam->viewmatrix_stride[0]; a.cs.v1 = vz ? 1 : cam->viewmatrix_stride[1];
-    a.cs.p0 = pz ? 4 : cam->projmatrix_stride[0]; a.cs.p1 = pz ? 1 : cam->projmatrix_stride[1];
-    a.cs.c0 = cam->campos_stride ? cam->campos_stride : 1;
+    v.cs.v0 = vz ? 4 : cam->viewmatrix_stride[0]; v.cs.v1 = vz ? 1 : cam->viewmatrix_stride[1];
+    v.cs.p0 = pz ? 4 : cam->projmatrix_stride[0]; v.cs.p1 = pz ? 1 : cam->projmatrix_stride[1];
+    v.cs.c0 = cam->campos_stride ? cam->campos_stride : 1;
 }
 
-void carve_geom(FwdArgs &a, char *base) {
-    const GeomLayout L(a.P);
-    a.depth = (float *)(base + L.depth); a.rec = (float4 *)(base + L.rec);
-    a.rect = (uint2 *)(base + L.rect); a.tiles = (uint32_t *)(base + L.tiles); a.goff = (uint32_t *)(base + L.goff);
-    a.clampm = (uint8_t *)(base + L.clampm);
+// GEOM and IMAGE: the state the forward saves for the backward (A: FwdArgs, or BwdArgs' const views) ...
+template <typename A>
+void carve_saved(A &a, char *geom, char *img) {
+    const GeomLayout G(a.v.P);
+    a.rec = (float4 *)(geom + G.rec); a.rect = (uint2 *)(geom + G.rect);
+    a.goff = (uint32_t *)(geom + G.goff); a.clampm = (uint8_t *)(geom + G.clampm);
+    const ImageLayout L(a.v.W, a.v.H, a.v.P);
+    a.ranges = (uint2 *)(img + L.ranges); a.pix_end = (float4 *)(img + L.pix_end);
+    a.n_contrib = (uint32_t *)(img + L.n_contrib); a.tile_maxc = (uint32_t *)(img + L.tile_maxc);
+    a.tile_flag = (uint32_t *)(img + L.tile_flag); a.near_rec = (float4 *)(img + L.near_rec);
+    a.seg_off = (uint32_t *)(img + L.seg_off); a.meta = (uint32_t *)(img + L.meta);
+    a.items_ws = (uint32_t *)(img + L.items_ws);
 }
-void carve_image(FwdArgs &a, char *base) {
-    const ImageLayout L(a.W, a.H, a.P);
-    a.ranges = (uint2 *)(base + L.ranges); a.pix_end = (float4 *)(base + L.pix_end);
-    a.n_contrib = (uint32_t *)(base + L.n_contrib); a.tile_maxc = (uint32_t *)(base + L.tile_maxc);
-    a.tile_order_f = (uint32_t *)(base + L.tile_order_f);
-    a.seg_off = (uint32_t *)(base + L.seg_off);
-    a.sort_lists = (uint32_t *)(base + L.sort_lists);
-    a.tile_count = (uint32_t *)(base + L.tile_count); a.tile_cursor = (uint32_t *)(base + L.tile_cursor);
-    a.block_sums = (uint32_t *)(base + L.block_sums); a.block_off = (uint32_t *)(base + L.block_off);
-    a.meta = (uint32_t *)(base + L.meta); a.chunk_off = (uint32_t *)(base + L.chunk_off);
-    a.items_ws = (uint32_t *)(base + L.items_ws);
-    a.scan_ws = (uint32_t *)(base + L.scan_ws); a.tile_rank = (uint32_t *)(base + L.tile_rank);
-    a.tile_flag = (uint32_t *)(base + L.tile_flag); a.near_rec = (float4 *)(base + L.near_rec);
-    a.tsat_list = (uint32_t *)(base + L.tsat_list);
+// ... and what only the forward's own kernels use
+void carve_forward(FwdArgs &a, char *geom, char *img) {
+    carve_saved(a, geom, img);
+    const GeomLayout G(a.v.P);
+    a.depth = (float *)(geom + G.depth); a.tiles = (uint32_t *)(geom + G.tiles);
+    const ImageLayout L(a.v.W, a.v.H, a.v.P);
+    a.tile_order_f = (uint32_t *)(img + L.tile_order_f); a.sort_lists = (uint32_t *)(img + L.sort_lists);
+    a.tile_count = (uint32_t *)(img + L.tile_count); a.tile_cursor = (uint32_t *)(img + L.tile_cursor);
+    a.block_sums = (uint32_t *)(img + L.block_sums); a.block_off = (uint32_t *)(img + L.block_off);
+    a.chunk_off = (uint32_t *)(img + L.chunk_off); a.scan_ws = (uint32_t *)(img + L.scan_ws);
+    a.tile_rank = (uint32_t *)(img + L.tile_rank); a.tsat_list = (uint32_t *)(img + L.tsat_list);
 }
-void carve_binning(FwdArgs &a, char *base, int K) {
-    const BinningLayout L(K, a.P);
-    a.pairs = (uint4 *)(base + L.pairs);
-    a.point_list = (uint32_t *)(base + L.point_list);
-    a.slot_emit = (uint32_t *)(base + L.slot_emit);
-    a.seg_state = (float4 *)(base + L.seg_state);
+template <typename A>
+void carve_binning(A &a, char *bin, const BinningLayout &L) {  // (+ FwdArgs::pairs, the forward's own)
+    a.point_list = (uint32_t *)(bin + L.point_list); a.slot_emit = (uint32_t *)(bin + L.slot_emit);
+    a.seg_state = (float4 *)(bin + L.seg_state);
+}
+
+// One BINNING allocation, laid out for K pairs (or a speculative capacity): the binning arrays, then
+// [the backward's item list] (prepare_backward), then [the merge buffer of the lists past kSortCap].
+struct BinRegions {
+    BinningLayout arrays;
+    size_t items, tmp, total;
+    BinRegions(int K, int P, int T, bool with_items, bool with_merge) : arrays(K, P) {
+        items = arrays.total;
+        tmp = items + (with_items ? bwd_items_bytes(K, T) : 0);
+        total = tmp + (with_merge ? sizeof(uint4) * (size_t)K : 0);
+    }
+};
+
+// The forward after k_bin_scan: BINNING carved at `bin` for `layout` pairs, then k_bin_emit -> the list
+// sorts -> k_render_fwd -> [the backward's item list].  `a` has GEOM and IMAGE carved.  Exact: `layout`
+// is K, with k_bin_scan's list classes.  Speculative (`spec_ok`: the forward's meta + 1, classes zero):
+// `layout` is the capacity; the kernels read K on the device and return when the scan's verdict failed.
+int enqueue_post_scan(FwdArgs a, char *bin, int layout, uint32_t n_mid, uint32_t n_vlong, uint32_t max_n,
+                      bool prepare_backward, int T, hipStream_t s, const uint32_t *spec_ok, bool phases) {
+    const BinRegions R(layout, a.v.P, T, prepare_backward, n_vlong != 0);
+    carve_binning(a, bin, R.arrays);
+    a.pairs = (uint4 *)(bin + R.arrays.pairs);
+    a.spec_ok = spec_ok;
+    uint4 *tmp = n_vlong ? (uint4 *)(bin + R.tmp) : nullptr;
+    uint2 *items = (uint2 *)(bin + R.items);
+    { Phase ph(s, "bin_emit", phases); HIP_TRY(launch_bin_emit(a, spec_ok ? 0 : layout, s)); }
+    { Phase ph(s, "tile_sort", phases); HIP_TRY(launch_tile_sort(a, n_mid, n_vlong, max_n, tmp, s)); }
+    { Phase ph(s, "render_fwd", phases); HIP_TRY(launch_render_fwd(a, s)); }
+    if (prepare_backward) {  // the backward's item list, built here, off its critical path
+        Phase ph(s, "bwd_items", phases);
+        HIP_TRY(launch_bwd_items_raw(layout, T, a.v.P, a.ranges, a.tile_maxc, a.tile_flag, items, a.items_ws, s, spec_ok));
+    }
+    return GSR_OK;
+}
+
+// Spins on the host-mapped word k_bin_scan publishes K into (the scan is queued behind the caller's
+// earlier work on the stream: this can take milliseconds).  Every ~0.5 ms the runtime is asked whether
+// the stream failed or drained (the word is read once more then): a faulted launch ends the spin.
+enum class KWait { published, stream_error, drained };
+KWait wait_published(const uint32_t *word, hipStream_t s, hipError_t *err) {
+    auto last = hclock::now();
+    while (__atomic_load_n(word, __ATOMIC_ACQUIRE) == kNoValue) {
+        __builtin_ia32_pause();
+        if (hclock::now() - last > std::chrono::microseconds(500)) {
+            last = hclock::now();
+            const hipError_t q = hipStreamQuery(s);
+            if (q == hipErrorNotReady) continue;
+            *err = q;
+            if (q != hipSuccess) return KWait::stream_error;
+            return __atomic_load_n(word, __ATOMIC_ACQUIRE) == kNoValue ? KWait::drained : KWait::published;
+        }
+    }
+    return KWait::published;
 }
 
 }  // namespace
@@ -529,22 +575,13 @@ int async_redo(AsyncFwd &f, hipStream_t H) {
     HIP_TRY(hipStreamWaitEvent(H, f.ev_scan, 0));
     const uint32_t *w = slot_h(f.slot);
     const uint32_t K = f.K, n_mid = w[1], n_vlong = w[2], max_n = w[3];
-    FwdArgs a = f.a;
-    a.spec_ok = nullptr;
-    a.spec_cap = 0;
-    const size_t bin_bytes = BinningLayout((int)K, a.P).total;
-    const size_t item_bytes = (f.prep) ? bwd_items_bytes((int)K, f.T) : 0;
-    const size_t tmp_bytes = n_vlong ? sizeof(uint4) * (size_t)K : 0;
+    const size_t bytes = BinRegions((int)K, f.a.v.P, f.T, f.prep, n_vlong != 0).total;
     void *bin = nullptr;
-    if (hipMallocAsync(&bin, bin_bytes + item_bytes + tmp_bytes, H) != hipSuccess || !bin)
-        return fail(GSR_ERR_ALLOC, "asynchronous forward: hipMallocAsync of %zu bytes failed", bin_bytes + item_bytes + tmp_bytes);
+    if (hipMallocAsync(&bin, bytes, H) != hipSuccess || !bin)
+        return fail(GSR_ERR_ALLOC, "asynchronous forward: hipMallocAsync of %zu bytes failed", bytes);
     f.own = bin;
-    carve_binning(a, (char *)bin, (int)K);
-    HIP_TRY(launch_bin_emit(a, (int)K, H));
-    HIP_TRY(launch_tile_sort(a, n_mid, n_vlong, max_n, (uint4 *)((char *)bin + bin_bytes + item_bytes), H));
-    HIP_TRY(launch_render_fwd(a, H));
-    if (f.prep)
-        HIP_TRY(launch_bwd_items_raw((int)K, f.T, a.P, a.ranges, a.tile_maxc, a.tile_flag, (uint2 *)((char *)bin + bin_bytes), a.items_ws, H));
+    const int rc = enqueue_post_scan(f.a, (char *)bin, (int)K, n_mid, n_vlong, max_n, f.prep, f.T, H, nullptr, false);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(H));
     f.bin = bin;
     f.layout = (int)K;
@@ -617,8 +654,7 @@ extern "C" size_t gsr_spec_binning_bytes(int P, int W, int H, int prepare_backwa
     (void)hipGetDevice(&dev);
     const uint32_t cap = spec_capacity(SpecKey{dev, P, W, H});
     if (!cap) return 0;
-    const size_t items = (prepare_backward) ? bwd_items_bytes((int)cap, div_up(W, kTileW) * div_up(H, kTileH)) : 0;
-    return BinningLayout((int)cap, P).total + items;
+    return BinRegions((int)cap, P, div_up(W, kTileW) * div_up(H, kTileH), prepare_backward != 0, false).total;
 }
 
 namespace {
@@ -639,21 +675,20 @@ int forward_impl(const gsr_camera *cam, const gsr_gaussians *g, gsr_alloc_fn all
     }
     hipStream_t s = (hipStream_t)stream;
     FwdArgs a;
-    fill_common(a, cam, g);
+    memset(&a, 0, sizeof(a));
+    fill_common(a.v, cam, g);
+    const int P = a.v.P, T = a.v.gx * a.v.gy;
+    const bool prep = g->prepare_backward != 0;
+    a.exact = g_exact.load(std::memory_order_relaxed);
     a.radii = out_radii; a.out_color = out_color; a.out_depth = out_depth;
-    const size_t npix = (size_t)a.W * a.H;
     // The three persistent buffers are always requested, so a caller can hand them back verbatim.
-    char *geom = (char *)alloc(alloc_ctx, GSR_BUF_GEOM, GeomLayout(a.P).total);
-    char *img = (char *)alloc(alloc_ctx, GSR_BUF_IMAGE, ImageLayout(a.W, a.H, a.P).total);
+    char *geom = (char *)alloc(alloc_ctx, GSR_BUF_GEOM, GeomLayout(P).total);
+    char *img = (char *)alloc(alloc_ctx, GSR_BUF_IMAGE, ImageLayout(a.v.W, a.v.H, P).total);
     if (!geom || !img) return fail(GSR_ERR_ALLOC, "allocation callback failed (geom/image)");
-    carve_geom(a, geom);
-    carve_image(a, img);
-    info->num_rendered = 0;
-    info->binning_layout = 0;
-    info->speculated = 0;
-    info->pending = 0;
-    info->aux_stream = nullptr;
-    if (a.P == 0) {  // reference: colour/depth stay zero (no background) when there are no Gaussians
+    carve_forward(a, geom, img);
+    *info = gsr_forward_info{};  // exact path, nothing rendered, nothing pending
+    if (P == 0) {  // reference: colour/depth stay zero (no background) when there are no Gaussians
+        const size_t npix = (size_t)a.v.W * a.v.H;
         HIP_TRY(launch_zero(out_color, 3 * npix, s));
         HIP_TRY(launch_zero(out_depth, npix, s));
         char *bin = (char *)alloc(alloc_ctx, GSR_BUF_BINNING, BinningLayout(0, 0).total);
@@ -662,12 +697,11 @@ int forward_impl(const gsr_camera *cam, const gsr_gaussians *g, gsr_alloc_fn all
     }
     int dev = 0;
     (void)hipGetDevice(&dev);
-    const SpecKey key{dev, a.P, a.W, a.H};
+    const SpecKey key{dev, P, a.v.W, a.v.H};
     uint32_t sort_blocks = kSpecSortBlocks;
     const uint32_t cap = mode ? spec_capacity(key, &sort_blocks) : 0u;
     a.spec_cap = cap;
     a.spec_sort_blocks = sort_blocks;
-    const int T = a.gx * a.gy;
     // where k_bin_scan publishes K: an asynchronous forward's ring slot, else this thread's word
     std::shared_ptr<AsyncFwd> af;
     uint32_t *words_h = nullptr, *words_d = nullptr;
@@ -677,10 +711,8 @@ int forward_impl(const gsr_camera *cam, const gsr_gaussians *g, gsr_alloc_fn all
             const int slot = slot_acquire();
             if (slot >= 0) {
                 af = std::make_shared<AsyncFwd>();
-                af->slot = slot;
-                af->seq = ++g_as_seq;
-                words_h = slot_h(slot);
-                words_d = slot_d(slot);
+                af->slot = slot; af->seq = ++g_as_seq;
+                words_h = slot_h(slot); words_d = slot_d(slot);
                 __atomic_store_n(words_h + kGateErrWord, 0u, __ATOMIC_RELAXED);
             }
         }
@@ -697,8 +729,7 @@ int forward_impl(const gsr_camera *cam, const gsr_gaussians *g, gsr_alloc_fn all
     if (!af) {
         HostWord hw = pinned_word();
         if (!hw.h) return fail(GSR_ERR_HIP, "hipHostMalloc(mapped) failed");
-        words_h = hw.h;
-        words_d = hw.d;
+        words_h = hw.h; words_d = hw.d;
     }
     __atomic_store_n(words_h, kNoValue, __ATOMIC_SEQ_CST);
     { Phase ph(s, "preprocess"); HIP_TRY(launch_preprocess(a, s)); }
@@ -712,68 +743,38 @@ int forward_impl(const gsr_camera *cam, const gsr_gaussians *g, gsr_alloc_fn all
         if (!af->ev_scan) HIP_TRY(hipEventCreateWithFlags(&af->ev_scan, hipEventDisableTiming | hipEventBlockingSync));
         HIP_TRY(hipEventRecord(af->ev_scan, s));
     }
-    const size_t spec_item_bytes = (g->prepare_backward) ? bwd_items_bytes((int)cap, T) : 0;
     char *spec_bin = nullptr;
     if (cap) {  // speculative: the post-scan kernels are queued now, against the capacity
-        spec_bin = (char *)alloc(alloc_ctx, GSR_BUF_BINNING, BinningLayout((int)cap, a.P).total + spec_item_bytes);
+        spec_bin = (char *)alloc(alloc_ctx, GSR_BUF_BINNING, BinRegions((int)cap, P, T, prep, false).total);
         if (!spec_bin) return fail(GSR_ERR_ALLOC, "allocation callback failed (binning, capacity %u)", cap);
         FwdArgs sa = a;
-        carve_binning(sa, spec_bin, (int)cap);
-        sa.spec_ok = sa.meta + 1;
         if (af) {  // a failed speculation holds the stream in the speculative render until it is redone
-            sa.gate = words_d + kGateWord;
-            sa.gate_seq = af->seq;
-            sa.gate_err = words_d + kGateErrWord;
-            sa.gate_timeout = g_gate_timeout;
+            sa.gate = words_d + kGateWord; sa.gate_seq = af->seq;
+            sa.gate_err = words_d + kGateErrWord; sa.gate_timeout = g_gate_timeout;
         }
-        { Phase ph(s, "bin_emit"); HIP_TRY(launch_bin_emit(sa, 0, s)); }
-        { Phase ph(s, "tile_sort"); HIP_TRY(launch_tile_sort(sa, 0, 0, 0, nullptr, s)); }
-        { Phase ph(s, "render_fwd"); HIP_TRY(launch_render_fwd(sa, s)); }
-        if (g->prepare_backward) {
-            uint2 *items = (uint2 *)(spec_bin + BinningLayout((int)cap, a.P).total);
-            Phase ph(s, "bwd_items");
-            HIP_TRY(launch_bwd_items_raw((int)cap, T, a.P, a.ranges, a.tile_maxc, a.tile_flag, items, a.items_ws, s, sa.spec_ok));
-        }
+        rc = enqueue_post_scan(sa, spec_bin, (int)cap, 0, 0, 0, prep, T, s, a.meta + 1, true);
+        if (rc) return rc;
     }
     if (af) {  // asynchronous: gate the stream on the verdict and return
         std::lock_guard<std::mutex> lk(g_as_mu);
         af->id = g_as_next_id++;
         af->dev = dev; af->s = s; af->cap = cap; af->T = T; af->key = key;
-        af->prep = g->prepare_backward != 0;
-        af->a = a;
-        af->spec_bin = spec_bin;
+        af->prep = prep; af->a = a; af->spec_bin = spec_bin;
         g_as[af->id] = af;
-        info->num_rendered = -1;
-        info->binning_layout = (int)cap;
-        info->speculated = 1;
-        info->pending = af->id;
-        {
-            std::lock_guard<std::mutex> lk2(g_spec_mu);
-            ++g_async_calls;
-        }
+        info->num_rendered = -1; info->binning_layout = (int)cap;
+        info->speculated = 1; info->pending = af->id;
+        { std::lock_guard<std::mutex> lk2(g_spec_mu); ++g_async_calls; }
         g_as_wake.notify_one();
         return GSR_OK;
     }
-    uint32_t K;
     {
         HostPhase hp("host_wait_K");
-        // Spin on the host-mapped word (the scan is queued behind the caller's earlier work on this
-        // stream, so this can take milliseconds).  Every ~0.5 ms ask the runtime whether the stream
-        // has drained or failed, so a faulted launch cannot leave us spinning.
-        auto last = hclock::now();
-        while ((K = __atomic_load_n(words_h, __ATOMIC_ACQUIRE)) == kNoValue) {
-            __builtin_ia32_pause();
-            if (hclock::now() - last > std::chrono::microseconds(500)) {
-                last = hclock::now();
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipErrorNotReady) continue;
-                if (q != hipSuccess) return fail(GSR_ERR_HIP, "stream error while waiting for num_rendered: %s", hipGetErrorString(q));
-                K = __atomic_load_n(words_h, __ATOMIC_ACQUIRE);
-                if (K == kNoValue) return fail(GSR_ERR_HIP, "num_rendered was not published");
-                break;
-            }
-        }
+        hipError_t q = hipSuccess;
+        const KWait w = wait_published(words_h, s, &q);
+        if (w == KWait::stream_error) return fail(GSR_ERR_HIP, "stream error while waiting for num_rendered: %s", hipGetErrorString(q));
+        if (w == KWait::drained) return fail(GSR_ERR_HIP, "num_rendered was not published");
     }
+    const uint32_t K = __atomic_load_n(words_h, __ATOMIC_ACQUIRE);
     if (K > 0x7FFFFFFFu) return fail(GSR_ERR_UNSUPPORTED, "num_rendered overflow");
     info->num_rendered = (int)K;
     // tiles to sort outside the render: [1] up to kSortCap pairs, [2] longer (merge sort), [3] the
@@ -788,22 +789,10 @@ int forward_impl(const gsr_camera *cam, const gsr_gaussians *g, gsr_alloc_fn all
         return GSR_OK;
     }
     // exact path (also the redo of a failed speculation: its queued kernels returned at once)
-    a.spec_ok = nullptr;
-    // BINNING = the binning arrays, [the backward's item list], [the long-list merge buffer]
-    const size_t bin_bytes = BinningLayout((int)K, a.P).total;
-    const size_t item_bytes = (g->prepare_backward) ? bwd_items_bytes((int)K, T) : 0;
-    const size_t tmp_bytes = n_vlong ? sizeof(uint4) * (size_t)K : 0;
-    char *bin = (char *)alloc(alloc_ctx, GSR_BUF_BINNING, bin_bytes + item_bytes + tmp_bytes);
+    char *bin = (char *)alloc(alloc_ctx, GSR_BUF_BINNING, BinRegions((int)K, P, T, prep, n_vlong != 0).total);
     if (!bin) return fail(GSR_ERR_ALLOC, "allocation callback failed (binning, K=%u)", K);
-    carve_binning(a, bin, (int)K);
-    { Phase ph(s, "bin_emit"); HIP_TRY(launch_bin_emit(a, (int)K, s)); }
-    { Phase ph(s, "tile_sort"); HIP_TRY(launch_tile_sort(a, n_mid, n_vlong, max_n, (uint4 *)(bin + bin_bytes + item_bytes), s)); }
-    { Phase ph(s, "render_fwd"); HIP_TRY(launch_render_fwd(a, s)); }
-    if (g->prepare_backward) {  // the backward's item list, built here, off its critical path
-        uint2 *items = (uint2 *)(bin + bin_bytes);
-        Phase ph(s, "bwd_items");
-        HIP_TRY(launch_bwd_items_raw((int)K, T, a.P, a.ranges, a.tile_maxc, a.tile_flag, items, a.items_ws, s));
-    }
+    rc = enqueue_post_scan(a, bin, (int)K, n_mid, n_vlong, max_n, prep, T, s, nullptr, true);
+    if (rc) return rc;
     info->binning_layout = (int)K;
     spec_record(key, K, n_vlong > 0, cap ? -1 : 0, n_mid);
     return GSR_OK;
@@ -843,7 +832,6 @@ int gsr_forward_resolve(unsigned long long handle, gsr_forward_resolution *out) 
     auto it = g_as.find(handle);
     if (it == g_as.end()) return fail(GSR_ERR_ARG, "gsr_forward_resolve: unknown or released forward %llu", handle);
     std::shared_ptr<AsyncFwd> f = it->second;
-    auto last = hclock::now();
     while (f->state == 0 || f->state == 2) {
         if (f->state == 0) {
             if (__atomic_load_n(slot_h(f->slot), __ATOMIC_ACQUIRE) != kNoValue) {
@@ -851,27 +839,17 @@ int gsr_forward_resolve(unsigned long long handle, gsr_forward_resolution *out) 
                 if (f->state == 2) g_as_wake.notify_one();  // the resolver redoes it
                 continue;
             }
-            // K not published yet: spin outside the lock, checking the stream for faults every ~0.5 ms
+            // K not published yet: spin outside the lock
             lk.unlock();
-            while (__atomic_load_n(slot_h(f->slot), __ATOMIC_ACQUIRE) == kNoValue) {
-                __builtin_ia32_pause();
-                if (hclock::now() - last > std::chrono::microseconds(500)) {
-                    last = hclock::now();
-                    const hipError_t q = hipStreamQuery(f->s);
-                    if (q == hipErrorNotReady) continue;
-                    if (__atomic_load_n(slot_h(f->slot), __ATOMIC_ACQUIRE) != kNoValue) break;
-                    lk.lock();
-                    if (f->state == 0) {
-                        f->state = -1;
-                        f->err = q == hipSuccess ? std::string("num_rendered was not published")
-                                                 : std::string("stream error: ") + hipGetErrorString(q);
-                        __atomic_store_n(slot_h(f->slot) + kGateWord, f->seq, __ATOMIC_RELEASE);
-                    }
-                    lk.unlock();
-                    break;
-                }
-            }
+            hipError_t q = hipSuccess;
+            const KWait w = wait_published(slot_h(f->slot), f->s, &q);
             lk.lock();
+            if (w != KWait::published && f->state == 0) {
+                f->state = -1;
+                f->err = w == KWait::drained ? std::string("num_rendered was not published")
+                                             : std::string("stream error: ") + hipGetErrorString(q);
+                __atomic_store_n(slot_h(f->slot) + kGateWord, f->seq, __ATOMIC_RELEASE);
+            }
             continue;
         }
         g_as_done.wait(lk);
@@ -976,38 +954,29 @@ int backward_render(const gsr_camera *cam, const gsr_gaussians *g, const int *ra
     // caller redoes the half once gsr_forward_resolve reports the forward redone
     const bool spec = num_rendered < 0;
     if (spec && g->binning_layout <= 0) return fail(GSR_ERR_ARG, "num_rendered < 0 without the forward's binning_layout");
-    FwdArgs f;
-    fill_common(f, cam, g);
-    carve_geom(f, (char *)geom);
-    carve_image(f, (char *)image);
+    memset(&a, 0, sizeof(a));
+    fill_common(a.v, cam, g);
+    const int P = a.v.P, T = a.v.gx * a.v.gy;
     // the BINNING layout the forward used: its capacity when it enqueued speculatively (gsr_forward_info)
     const int layout = g->binning_layout > 0 ? g->binning_layout : num_rendered;
     if (layout < num_rendered) return fail(GSR_ERR_ARG, "binning_layout %d < num_rendered %d", layout, num_rendered);
     if (spec) num_rendered = layout;  // the bound every size below is taken from
-    carve_binning(f, (char *)binning, layout);
-    memset(&a, 0, sizeof(a));
-    a.P = f.P; a.D = f.D; a.M = f.M; a.W = f.W; a.H = f.H; a.gx = f.gx; a.gy = f.gy; a.K = num_rendered;
-    a.act = f.act;
-    a.scale_modifier = f.scale_modifier; a.tan_fovx = f.tan_fovx; a.tan_fovy = f.tan_fovy;
-    a.focal_x = f.focal_x; a.focal_y = f.focal_y;
-    a.means3D = f.means3D; a.scales = f.scales; a.rotations = f.rotations; a.shs = f.shs;
-    a.colors_precomp = f.colors_precomp; a.cov3D_precomp = f.cov3D_precomp;
-    a.viewmatrix = f.viewmatrix; a.projmatrix = f.projmatrix; a.campos = f.campos; a.bg = f.bg; a.cs = f.cs;
+    a.K = num_rendered;
     a.radii = radii;
-    a.rec = f.rec; a.rect = f.rect; a.goff = f.goff; a.clampm = f.clampm;
-    a.ranges = f.ranges; a.pix_end = f.pix_end; a.n_contrib = f.n_contrib; a.tile_maxc = f.tile_maxc;
-    a.tile_flag = f.tile_flag; a.near_rec = f.near_rec;
-    a.seg_off = f.seg_off; a.meta = f.meta; a.items_ws = f.items_ws;
-    a.point_list = f.point_list; a.slot_emit = f.slot_emit; a.seg_state = f.seg_state;
+    // the forward's saved state: const views of GEOM, IMAGE and BINNING
+    const BinRegions BR(layout, P, T, g->prepare_backward != 0, false);
+    char *bb = (char *)binning;
+    carve_saved(a, (char *)geom, (char *)image);
+    carve_binning(a, bb, BR.arrays);
     a.dL_dcolor = dL_dcolor;
-    a.spec_ok = spec ? f.meta + 1 : nullptr;
-    const ScratchLayout SL(num_rendered, a.gx * a.gy);
+    a.spec_ok = spec ? a.meta + 1 : nullptr;
+    const ScratchLayout SL(num_rendered, T);
     char *scr = (char *)alloc(alloc_ctx, GSR_BUF_SCRATCH, SL.total);
     if (!scr) return fail(GSR_ERR_ALLOC, "allocation callback failed (scratch)");
     a.part = (float4 *)(scr + SL.part);
-    a.max_items = (uint32_t)max_bwd_items(num_rendered, a.gx * a.gy);
+    a.max_items = (uint32_t)max_bwd_items(num_rendered, T);
     if (g->prepare_backward) {  // built by the forward, after the binning arrays
-        a.items = (uint2 *)((char *)binning + BinningLayout(layout, a.P).total);
+        a.items = (uint2 *)(bb + BR.items);
     } else {
         a.items = (uint2 *)(scr + SL.items);
         Phase ph(s, "bwd_items");
@@ -1015,10 +984,11 @@ int backward_render(const gsr_camera *cam, const gsr_gaussians *g, const int *ra
     }
     { Phase ph(s, "render_bwd"); HIP_TRY(launch_render_bwd(a, s)); }
     if (sums) {  // deferred view: its per-Gaussian record sums for gsr_backward_gaussians (SUMS buffer)
-        float *out = (float *)alloc(alloc_ctx, GSR_BUF_SUMS, gsr_sums_bytes(a.P));
+        float *out = (float *)alloc(alloc_ctx, GSR_BUF_SUMS, gsr_sums_bytes(P));
         if (!out) return fail(GSR_ERR_ALLOC, "allocation callback failed (sums)");
         Phase ph(s, "sum_records");
-        HIP_TRY(launch_sum_records(a.P, a.goff, a.part, out, s, a.spec_ok, a.viewmatrix, a.projmatrix, a.campos, a.cs, a.W, a.H));
+        HIP_TRY(launch_sum_records(P, a.goff, a.part, out, s, a.spec_ok, a.v.viewmatrix, a.v.projmatrix, a.v.campos, a.v.cs,
+                                   a.v.W, a.v.H));
     }
     return GSR_OK;
 }
@@ -1097,7 +1067,7 @@ int gsr_backward_gaussians(int nviews, const gsr_view_grad *views, const gsr_gau
         for (int k = 0; k < m.nv; ++k) {
             const gsr_view_grad &vg = views[v0 + k];
             const gsr_camera *cam = vg.cam;
-            FwdArgs f;
+            ViewIn f;
             fill_common(f, cam, g);
             MultiView &mv = m.v[k];
             mv.viewmatrix = cam->viewmatrix; mv.projmatrix = cam->projmatrix; mv.campos = cam->campos;
@@ -1128,334 +1098,6 @@ int gsr_mark_visible(int P, const float *means3D, const float *viewmatrix, const
     if (P < 0) return fail(GSR_ERR_ARG, "P must be >= 0");
     if (P > 0 && (!means3D || !viewmatrix || !present)) return fail(GSR_ERR_ARG, "null pointer");
     HIP_TRY(launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream));
-    return GSR_OK;
-}
-
-}  // extern "C"
-
-// ---- fused L1 + SSIM ----------------------------------------------------------------------
-namespace {
-struct SsimScratch {
-    size_t maps, partial, total;
-    SsimScratch(int planes, int H, int W) {
-        const size_t n = (size_t)planes * H * W;
-        maps = 0;
-        partial = align256(sizeof(float) * 3 * n);
-        total = align256(partial + sizeof(float2) * ssim_partials(planes, H, W));
-    }
-};
-
-// The window of calc_ssim: gaussian(11, 1.5) (external.py:48-55) evaluates exp() in double, stores
-// float32 and normalises by the float32 sum.
-SsimWindow ssim_window() {
-    SsimWindow w;
-    float sum = 0.f;
-    for (int x = 0; x < 11; ++x) {
-        w.w[x] = (float)std::exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5));
-        sum += w.w[x];
-    }
-    for (int x = 0; x < 11; ++x) w.w[x] = w.w[x] / sum;
-    return w;
-}
-
-int check_ssim(int planes, int H, int W, const float *img1, const float *img2) {
-    if (planes < 0 || H < 0 || W < 0) return fail(GSR_ERR_ARG, "l1_ssim: negative size");
-    if ((size_t)planes * H * W > 0 && (!img1 || !img2)) return fail(GSR_ERR_ARG, "l1_ssim: null image");
-    if ((size_t)planes * H * W >= (size_t)1 << 31) return fail(GSR_ERR_UNSUPPORTED, "l1_ssim: image too large");
-    if (planes > 65535) return fail(GSR_ERR_UNSUPPORTED, "l1_ssim: more than 65535 planes");
-    return GSR_OK;
-}
-}  // namespace
-
-extern "C" {
-
-size_t gsr_ssim_scratch_bytes(int planes, int H, int W) {
-    return SsimScratch(planes < 0 ? 0 : planes, H < 0 ? 0 : H, W < 0 ? 0 : W).total;
-}
-
-int gsr_l1_ssim_forward(int planes, int H, int W, const float *img1, const float *img2, void *scratch,
-                        float *out_l1, float *out_ssim, void *stream) {
-    int rc = check_ssim(planes, H, W, img1, img2);
-    if (rc) return rc;
-    if (!out_l1 || !out_ssim) return fail(GSR_ERR_ARG, "l1_ssim: null output");
-    if ((size_t)planes * H * W == 0) return fail(GSR_ERR_ARG, "l1_ssim: empty image (the mean is undefined)");
-    if (!scratch) return fail(GSR_ERR_ARG, "l1_ssim: null scratch");
-    hipStream_t s = (hipStream_t)stream;
-    const SsimScratch L(planes, H, W);
-    char *base = (char *)scratch;
-    Phase ph(s, "ssim_fwd");
-    HIP_TRY(launch_ssim_fwd(planes, H, W, img1, img2, ssim_window(), (float *)(base + L.maps),
-                            (float2 *)(base + L.partial), out_l1, out_ssim, s));
-    return GSR_OK;
-}
-
-int gsr_l1_ssim_backward(int planes, int H, int W, const float *img1, const float *img2, const void *scratch,
-                         const float *dL_dl1, const float *dL_dssim, float *dL_dimg1, void *stream) {
-    int rc = check_ssim(planes, H, W, img1, img2);
-    if (rc) return rc;
-    if ((size_t)planes * H * W == 0) return GSR_OK;
-    if (!dL_dimg1 || !scratch) return fail(GSR_ERR_ARG, "l1_ssim: null gradient output / scratch");
-    hipStream_t s = (hipStream_t)stream;
-    const SsimScratch L(planes, H, W);
-    Phase ph(s, "ssim_bwd");
-    HIP_TRY(launch_ssim_bwd(planes, H, W, img1, img2, ssim_window(), (const float *)((const char *)scratch + L.maps),
-                            dL_dl1, dL_dssim, dL_dimg1, s));
-    return GSR_OK;
-}
-
-// ---- rigidity loss + k-nearest neighbours ---------------------------------------------------
-}  // extern "C"
-namespace {
-constexpr int kKnnMaxK = 32;
-struct RigidScratch {
-    size_t partial, save_m, save_q, save_u, total;
-    RigidScratch(int F, int k, bool save) {
-        const size_t f = (size_t)F;
-        partial = 0;
-        size_t o = align256(sizeof(double) * (size_t)rigid_blocks(F));
-        save_m = o; if (save) o = align256(o + sizeof(float) * 3 * f);
-        save_q = o; if (save) o = align256(o + sizeof(float) * 4 * f);
-        save_u = o; if (save) o = align256(o + sizeof(float) * 3 * f * (size_t)k);
-        total = o;
-    }
-};
-int check_rigid(int P, int F, int k) {
-    if (P < 0 || F < 0 || k < 0) return fail(GSR_ERR_ARG, "rigidity: negative size");
-    if (F > P) return fail(GSR_ERR_ARG, "rigidity: %d foreground rows of %d Gaussians", F, P);
-    if ((size_t)F * (size_t)k >= (size_t)1 << 31) return fail(GSR_ERR_UNSUPPORTED, "rigidity: more than 2^31 edges");
-    return GSR_OK;
-}
-}  // namespace
-extern "C" {
-
-int gsr_knn(int n, const float *points, int k, int *out_indices, double *out_sq_distances, void *stream) {
-    if (n < 0 || k < 1) return fail(GSR_ERR_ARG, "knn: n must be >= 0 and k >= 1 (got n = %d, k = %d)", n, k);
-    if (k > kKnnMaxK) return fail(GSR_ERR_UNSUPPORTED, "knn: k = %d (at most %d supported)", k, kKnnMaxK);
-    if (n <= k) return fail(GSR_ERR_ARG, "knn: %d points have no %d other points each", n, k);
-    if ((size_t)n * (size_t)k >= (size_t)1 << 31) return fail(GSR_ERR_UNSUPPORTED, "knn: more than 2^31 results");
-    if (!points || !out_indices || !out_sq_distances) return fail(GSR_ERR_ARG, "knn: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    Phase ph(s, "knn");
-    HIP_TRY(launch_knn(n, points, k, out_indices, out_sq_distances, s));
-    return GSR_OK;
-}
-
-size_t gsr_rigidity_scratch_bytes(int F, int k, int save_for_backward) {
-    return RigidScratch(F < 0 ? 0 : F, k < 0 ? 0 : k, save_for_backward != 0).total;
-}
-
-int gsr_rigidity_forward(int P, int F, int k, const float *means, const float *rotation_quaternions,
-                         const int *foreground_rows, const int *neighbor_rows, const float *weights,
-                         const float *previous_offsets, const float *previous_inverted_rotations, void *scratch,
-                         int save_for_backward, float *out_loss, void *stream) {
-    int rc = check_rigid(P, F, k);
-    if (rc) return rc;
-    if (F == 0 || k == 0) return fail(GSR_ERR_ARG, "rigidity: no foreground edges (the mean is undefined)");
-    if (!means || !rotation_quaternions || !foreground_rows || !neighbor_rows || !weights || !previous_offsets ||
-        !previous_inverted_rotations || !scratch || !out_loss)
-        return fail(GSR_ERR_ARG, "rigidity: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const RigidScratch L(F, k, save_for_backward != 0);
-    char *base = (char *)scratch;
-    const bool sv = save_for_backward != 0;
-    Phase ph(s, "rigidity_fwd");
-    HIP_TRY(launch_rigid_fwd(F, k, means, rotation_quaternions, foreground_rows, neighbor_rows, weights,
-                             previous_offsets, previous_inverted_rotations, (double *)(base + L.partial),
-                             sv ? (float *)(base + L.save_u) : nullptr, sv ? (float *)(base + L.save_m) : nullptr,
-                             sv ? (float *)(base + L.save_q) : nullptr, out_loss, s));
-    return GSR_OK;
-}
-
-int gsr_rigidity_backward(int P, int F, int k, const int *row_to_foreground, const int *reverse_offsets,
-                          const int *reverse_edges, const void *scratch, const float *dL_dloss, float *dL_dmeans,
-                          float *dL_drotation_quaternions, void *stream) {
-    int rc = check_rigid(P, F, k);
-    if (rc) return rc;
-    if (P == 0 || (!dL_dmeans && !dL_drotation_quaternions)) return GSR_OK;
-    if (F == 0 || k == 0) return fail(GSR_ERR_ARG, "rigidity: no foreground edges");
-    if (!row_to_foreground || !reverse_offsets || !reverse_edges || !scratch || !dL_dloss)
-        return fail(GSR_ERR_ARG, "rigidity: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const RigidScratch L(F, k, true);
-    const char *base = (const char *)scratch;
-    Phase ph(s, "rigidity_bwd");
-    HIP_TRY(launch_rigid_bwd(P, F, k, row_to_foreground, reverse_offsets, reverse_edges,
-                             (const float *)(base + L.save_u), (const float *)(base + L.save_m),
-                             (const float *)(base + L.save_q), dL_dloss, dL_dmeans, dL_drotation_quaternions, s));
-    return GSR_OK;
-}
-
-// ---- densification --------------------------------------------------------------------------
-}  // extern "C"
-namespace {
-int dens_args(const gsr_densify_settings *st, DensArgs &a) {
-    if (!st) return fail(GSR_ERR_ARG, "densify: null settings");
-    if (st->P < 0) return fail(GSR_ERR_ARG, "densify: P must be >= 0");
-    if (st->P > 0 && (!st->grad_accum || !st->vis_count || !st->log_scales || !st->opacity_logits ||
-                      !st->rotation_quaternions))
-        return fail(GSR_ERR_ARG, "densify: statistics / log_scales / opacity_logits / rotations required");
-    if (!(st->split_divisor > 0.f)) return fail(GSR_ERR_ARG, "densify: split_divisor must be > 0");
-    a.P = st->P; a.prune_big = st->prune_big;
-    a.grad_threshold = st->grad_threshold; a.small_scale = st->small_scale; a.big_scale = st->big_scale;
-    a.remove_opacity = st->remove_opacity;
-    // torch evaluates tensor / python-scalar on the GPU as tensor * (1 / scalar) in float
-    a.inv_split_div = 1.0f / st->split_divisor;
-    a.grad_accum = st->grad_accum; a.vis_count = st->vis_count; a.log_scales = st->log_scales;
-    a.opacity_logits = st->opacity_logits; a.rotations = st->rotation_quaternions;
-    return GSR_OK;
-}
-}  // namespace
-extern "C" {
-
-int gsr_densify_update_radii(int P, const int *radii, float *max_radii, uint8_t *visible, void *stream) {
-    if (P < 0) return fail(GSR_ERR_ARG, "densify: P must be >= 0");
-    if (P > 0 && (!radii || !max_radii || !visible)) return fail(GSR_ERR_ARG, "densify: null pointer");
-    HIP_TRY(launch_dens_radii(P, radii, max_radii, visible, (hipStream_t)stream));
-    return GSR_OK;
-}
-
-int gsr_densify_accumulate_grads(int P, const uint8_t *visible, const float *means2D_grad, float *grad_accum,
-                                 float *vis_count, void *stream) {
-    if (P < 0) return fail(GSR_ERR_ARG, "densify: P must be >= 0");
-    if (P > 0 && (!visible || !means2D_grad || !grad_accum || !vis_count))
-        return fail(GSR_ERR_ARG, "densify: null pointer");
-    HIP_TRY(launch_dens_grads(P, visible, means2D_grad, grad_accum, vis_count, (hipStream_t)stream));
-    return GSR_OK;
-}
-
-size_t gsr_densify_workspace_bytes(int P) { return DensWorkspace(P < 0 ? 0 : P).total; }
-
-int gsr_densify_plan(const gsr_densify_settings *st, void *workspace, gsr_densify_counts *counts, void *stream) {
-    DensArgs a;
-    int rc = dens_args(st, a);
-    if (rc) return rc;
-    if (!workspace || !counts) return fail(GSR_ERR_ARG, "densify: null workspace / counts");
-    memset(counts, 0, sizeof(*counts));
-    if (a.P == 0) return GSR_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const DensWorkspace L(a.P);
-    { Phase ph(s, "densify_plan"); HIP_TRY(launch_dens_plan(a, (char *)workspace, s)); }
-    uint32_t tot[4];
-    HIP_TRY(hipMemcpyAsync(tot, (char *)workspace + L.totals, sizeof(tot), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    counts->n_keep_orig = (int)tot[0];
-    counts->n_keep_clone = (int)tot[1];
-    counts->n_split = (int)tot[2];
-    counts->n_keep_split = (int)tot[3];
-    const long long po = (long long)tot[0] + tot[1] + 2ll * tot[3];
-    if (po > 0x7FFFFFFF) return fail(GSR_ERR_UNSUPPORTED, "densify: output too large");
-    counts->P_out = (int)po;
-    return GSR_OK;
-}
-
-int gsr_densify_split_stds(const gsr_densify_settings *st, const void *workspace, float *stds, void *stream) {
-    DensArgs a;
-    int rc = dens_args(st, a);
-    if (rc) return rc;
-    if (a.P == 0) return GSR_OK;
-    if (!workspace || !stds) return fail(GSR_ERR_ARG, "densify: null workspace / stds");
-    HIP_TRY(launch_dens_stds(a, (const char *)workspace, stds, (hipStream_t)stream));
-    return GSR_OK;
-}
-
-int gsr_densify_apply(const gsr_densify_settings *st, const void *workspace, const gsr_densify_counts *counts,
-                      const float *samples, int ncols, const gsr_densify_column *cols, void *stream) {
-    DensArgs a;
-    int rc = dens_args(st, a);
-    if (rc) return rc;
-    if (ncols < 0 || ncols > kDensMaxColumns) return fail(GSR_ERR_ARG, "densify: 0..%d columns", kDensMaxColumns);
-    if (a.P == 0 || ncols == 0) return GSR_OK;
-    if (!workspace || !cols || !counts) return fail(GSR_ERR_ARG, "densify: null workspace / counts / columns");
-    if (counts->n_split > 0 && !samples) return fail(GSR_ERR_ARG, "densify: %d splits need samples", counts->n_split);
-    DensColumns dc;
-    memset(&dc, 0, sizeof(dc));
-    dc.n = ncols;
-    for (int k = 0; k < ncols; ++k) {
-        const gsr_densify_column &c = cols[k];
-        if (c.width <= 0 || !c.src || !c.dst) return fail(GSR_ERR_ARG, "densify: column %d has no data", k);
-        if ((c.exp_avg == nullptr) != (c.exp_avg_sq == nullptr) || (c.exp_avg == nullptr) != (c.dst_exp_avg == nullptr) ||
-            (c.dst_exp_avg == nullptr) != (c.dst_exp_avg_sq == nullptr))
-            return fail(GSR_ERR_ARG, "densify: column %d: Adam moments must be given together", k);
-        if (c.role == GSR_DENS_MEANS && c.width != 3) return fail(GSR_ERR_ARG, "densify: means need width 3");
-        if (c.role == GSR_DENS_LOG_SCALES && c.width != 3) return fail(GSR_ERR_ARG, "densify: log_scales need width 3");
-        dc.c[k] = DensColumn{c.width, c.role, c.src, c.exp_avg, c.exp_avg_sq, c.dst, c.dst_exp_avg, c.dst_exp_avg_sq};
-    }
-    hipStream_t s = (hipStream_t)stream;
-    Phase ph(s, "densify_apply");
-    HIP_TRY(launch_dens_apply(a, (const char *)workspace, samples, dc, s));
-    return GSR_OK;
-}
-
-int gsr_adam_step(int ntensors, const gsr_adam_tensor *tensors, double beta1, double beta2, double eps,
-                  void *stream) {
-    if (ntensors < 0 || (ntensors > 0 && !tensors)) return fail(GSR_ERR_ARG, "adam: bad tensor list");
-    hipStream_t s = (hipStream_t)stream;
-    for (int k = 0; k < ntensors; ++k) {  // validate everything before launching anything
-        const gsr_adam_tensor &a = tensors[k];
-        if (a.numel < 0) return fail(GSR_ERR_ARG, "adam: tensor %d: negative numel", k);
-        if (a.numel > 0 && (!a.param || !a.grad || !a.exp_avg || !a.exp_avg_sq))
-            return fail(GSR_ERR_ARG, "adam: tensor %d: null pointer", k);
-        if (a.numel > 0 && !(a.step >= 1.0)) return fail(GSR_ERR_ARG, "adam: tensor %d: step must be >= 1", k);
-        if (adam_blocks(a.numel) > (1 << 30)) return fail(GSR_ERR_UNSUPPORTED, "adam: tensor %d too large", k);
-    }
-    Phase ph(s, "adam");
-    AdamTable tab;
-    auto reset = [&]() {
-        memset(&tab, 0, sizeof(tab));
-        tab.w1 = (float)(1.0 - beta1);
-        tab.b2 = (float)beta2;
-        tab.omb2 = (float)(1.0 - beta2);
-        tab.eps = (float)eps;
-    };
-    reset();
-    int nb = 0;
-    for (int k = 0; k < ntensors; ++k) {
-        const gsr_adam_tensor &a = tensors[k];
-        if (a.numel == 0) continue;
-        const int b = adam_blocks(a.numel);
-        if (tab.n == kAdamMaxTensors || nb + (long long)b > (1ll << 30)) {  // table full: launch it
-            tab.block_start[tab.n] = nb;
-            HIP_TRY(launch_adam(tab, s));
-            reset();
-            nb = 0;
-        }
-        const double bc1 = 1.0 - std::pow(beta1, a.step), bc2 = 1.0 - std::pow(beta2, a.step);
-        AdamTensor &t = tab.t[tab.n];
-        t.param = a.param; t.grad = a.grad; t.exp_avg = a.exp_avg; t.exp_avg_sq = a.exp_avg_sq;
-        t.n = a.numel;
-        t.step_size = (float)((a.lr / bc1) * -1.0);
-        t.bc2_sqrt = (float)std::pow(bc2, 0.5);
-        const uintptr_t al = (uintptr_t)a.param | (uintptr_t)a.grad | (uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq;
-        t.vec4 = (al & 15) == 0;
-        tab.block_start[tab.n] = nb;
-        nb += b;
-        ++tab.n;
-    }
-    if (tab.n) {
-        tab.block_start[tab.n] = nb;
-        HIP_TRY(launch_adam(tab, s));
-    }
-    return GSR_OK;
-}
-
-int gsr_views_pack(int frames, int H, int W, const uint8_t *rgb, const uint8_t *seg, float *images,
-                   float *seg_masks, void *stream) {
-    if (frames < 0 || H < 0 || W < 0) return fail(GSR_ERR_ARG, "views_pack: negative size");
-    if (frames == 0 || H == 0 || W == 0) return GSR_OK;
-    if ((long long)H * W > (1ll << 29)) return fail(GSR_ERR_UNSUPPORTED, "views_pack: frame of %d x %d too large", H, W);
-    if (frames > 65535) return fail(GSR_ERR_UNSUPPORTED, "views_pack: more than 65535 frames in one call");
-    if (!rgb || !images) return fail(GSR_ERR_ARG, "views_pack: null rgb / images");
-    if ((seg == nullptr) != (seg_masks == nullptr))
-        return fail(GSR_ERR_ARG, "views_pack: seg and seg_masks must be given together");
-    const int HW = H * W;
-    if (HW % 4 == 0) {  // the vector path's alignment contract
-        if (((uintptr_t)rgb & 3) || (seg && ((uintptr_t)seg & 3)) || ((uintptr_t)images & 15) ||
-            (seg_masks && ((uintptr_t)seg_masks & 15)))
-            return fail(GSR_ERR_ARG, "views_pack: rgb / seg must be 4-byte and outputs 16-byte aligned");
-    }
-    hipStream_t s = (hipStream_t)stream;
-    Phase ph(s, "views_pack");
-    HIP_TRY(launch_views_pack(frames, HW, rgb, seg, images, seg_masks, s));
     return GSR_OK;
 }
 

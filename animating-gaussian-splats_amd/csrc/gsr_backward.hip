@@ -23,7 +23,7 @@ __device__ uint64_t *g_trace_bwd;
 
 constexpr uint32_t kItemStartCost = 64;  // init loads + first gathers, in (pair, quarter) steps
 
-// The same item list built over the whole chip (the single block above runs on ONE CU: ~30 us at C3,
+// The backward's item list, built over the whole chip (a single block ran on ONE CU: ~30 us at C3,
 // 21 at C2, on the view's critical path).  k_items_count: one thread per tile counts its items per cost
 // bucket in an LDS histogram, the block adds its non-zero buckets into the workspace's global counts,
 // and the last block to finish (a done counter) turns the counts into the buckets' cursors (exclusive
@@ -1089,10 +1089,10 @@ template <int MC>
 constexpr size_t multi_lds_bytes() { return sizeof(float) * multi_sh_floats<MC>(); }
 
 // The order the launch sums its views in: fixed by their cameras -- the key
-// k_sum_records stored after each view's sums (a hash of its view matrix and camera position), ties (the
-// same camera twice) in queue order -- not by the order the backward pass queued them, so a caller whose
-// threads finish their forwards in a varying order gets the same gradients bit for bit.  Position t's
-// view is bits 4t..4t+3.  Wave-uniform: nv scalar loads and scalar compares.
+// k_sum_records stored after each view's sums (a hash of its view matrix, projection matrix, camera
+// position, W and H), ties (the same camera twice) in queue order -- not by the order the backward pass
+// queued them, so a caller whose threads finish their forwards in a varying order gets the same
+// gradients bit for bit.  Position t's view is bits 4t..4t+3.  Wave-uniform: nv scalar loads and scalar compares.
 static_assert(kMultiViews <= 8, "view order packed 4 bits per position");
 __device__ inline uint32_t view_order(const MultiArgs &a) {
     typedef const __attribute__((address_space(4))) uint32_t *key_ptr;
@@ -1356,7 +1356,7 @@ hipError_t launch_bwd_items_raw(int K, int T, int P, const uint2 *ranges, const 
     return hipGetLastError();
 }
 hipError_t launch_bwd_items(const BwdArgs &a, hipStream_t s) {
-    return launch_bwd_items_raw(a.K, a.gx * a.gy, a.P, a.ranges, a.tile_maxc, a.tile_flag, a.items, a.items_ws, s);
+    return launch_bwd_items_raw(a.K, a.v.gx * a.v.gy, a.v.P, a.ranges, a.tile_maxc, a.tile_flag, a.items, a.items_ws, s);
 }
 
 hipError_t launch_render_bwd(const BwdArgs &a, hipStream_t s) {
@@ -1365,12 +1365,12 @@ hipError_t launch_render_bwd(const BwdArgs &a, hipStream_t s) {
     // item exit at once.  Then the items of the tiles whose near-threshold records overflowed (tile_flag
     // > kNearCap; none when the exact-threshold mode is off) on a small grid that loops over their
     // device-side count.
-    const int ks = seg_log2(a.P);
+    const int ks = seg_log2(a.v.P);
     k_render_bwd<false><<<div_up((int)a.max_items, kBwdWaves), 64 * kBwdWaves, 0, s>>>(
-        a.W, a.H, a.gx, a.items, a.ranges, a.point_list, a.rec, a.bg, a.pix_end, a.n_contrib, a.tile_maxc, a.seg_off,
+        a.v.W, a.v.H, a.v.gx, a.items, a.ranges, a.point_list, a.rec, a.v.bg, a.pix_end, a.n_contrib, a.tile_maxc, a.seg_off,
         a.seg_state, a.slot_emit, a.dL_dcolor, a.part, ks, a.spec_ok, a.tile_flag, a.near_rec);
     k_render_bwd<true><<<std::min(div_up((int)a.max_items, kBwdWaves), kExactBwdBlocks), 64 * kBwdWaves, 0, s>>>(
-        a.W, a.H, a.gx, a.items, a.ranges, a.point_list, a.rec, a.bg, a.pix_end, a.n_contrib, a.tile_maxc, a.seg_off,
+        a.v.W, a.v.H, a.v.gx, a.items, a.ranges, a.point_list, a.rec, a.v.bg, a.pix_end, a.n_contrib, a.tile_maxc, a.seg_off,
         a.seg_state, a.slot_emit, a.dL_dcolor, a.part, ks, a.spec_ok, a.tile_flag, a.near_rec);
     return hipGetLastError();
 }
@@ -1379,16 +1379,16 @@ template <int MC>
 static void gauss_bwd_mc(const BwdArgs &a, hipStream_t s) {
     constexpr size_t lds = std::max(sizeof(float) * kShBlock * (MC ? sh_row_stride(MC) : 0),
                                     sizeof(float4) * kRecStageF4<MC> * (kShBlock / 64));
-    k_gauss_bwd<MC><<<div_up(a.P, kShBlock), kShBlock, lds, s>>>(
-        a.P, a.D, a.M, a.W, a.H, a.scale_modifier, a.tan_fovx, a.tan_fovy, a.focal_x, a.focal_y,
-        a.means3D, a.scales, a.rotations, a.shs, a.cov3D_precomp, a.viewmatrix, a.projmatrix, a.campos, a.cs,
+    k_gauss_bwd<MC><<<div_up(a.v.P, kShBlock), kShBlock, lds, s>>>(
+        a.v.P, a.v.D, a.v.M, a.v.W, a.v.H, a.v.scale_modifier, a.v.tan_fovx, a.v.tan_fovy, a.v.focal_x, a.v.focal_y,
+        a.v.means3D, a.v.scales, a.v.rotations, a.v.shs, a.v.cov3D_precomp, a.v.viewmatrix, a.v.projmatrix, a.v.campos, a.v.cs,
         a.radii, a.goff, a.part, a.dL_dmeans2D, a.dL_dcolors, a.dL_dopacity,
-        a.dL_dmeans3D, a.dL_dcov3D, a.dL_dsh, a.dL_dscales, a.dL_drot, a.act, a.rec, a.accm, a.clampm);
+        a.dL_dmeans3D, a.dL_dcov3D, a.dL_dsh, a.dL_dscales, a.dL_drot, a.v.act, a.rec, a.accm, a.clampm);
 }
 
 hipError_t launch_gauss_bwd(const BwdArgs &a, hipStream_t s) {
-    if (a.P == 0) return hipSuccess;
-    switch (a.shs ? a.M : 0) {
+    if (a.v.P == 0) return hipSuccess;
+    switch (a.v.shs ? a.v.M : 0) {
         case 16: gauss_bwd_mc<16>(a, s); break;
         case 9: gauss_bwd_mc<9>(a, s); break;
         case 4: gauss_bwd_mc<4>(a, s); break;

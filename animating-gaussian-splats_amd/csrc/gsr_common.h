@@ -225,7 +225,8 @@ __host__ __device__ inline size_t bwd_items_bytes(int K, int T) { return align25
 // SCRATCH (backward): one packed 36-byte partial-gradient record per Gaussian-tile pair, stored at
 // the pair's EMISSION index (Gaussian-major), so each Gaussian's records are contiguous for the
 // per-Gaussian reduction: dmean2D.xy, dconic.abc, dopacity, dcolour.rgb; then the backward's work
-// items ([0].x = count, then (tile, segment) in dispatch order, built by k_bwd_items).
+// items ([0].x = count, then (tile, segment) in dispatch order, built by k_items_count +
+// k_items_emit).
 struct ScratchLayout {
     size_t part, items, total;
     __host__ __device__ ScratchLayout(int K, int T) {
@@ -544,18 +545,6 @@ __device__ inline uint32_t block_excl_scan_u32(uint32_t v, uint32_t *lds, uint32
     return woff + inc - v;
 }
 
-// Sum of v over the 64 lanes of the wave, valid in lane 63 (gfx9 DPP row ops + row broadcasts).
-__device__ inline float wave_sum_lane63(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));  // quad_perm 1,0,3,2
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));  // quad_perm 2,3,0,1
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xF, 0xF, false)); // row_ror:4
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false)); // row_ror:8
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false)); // row_bcast:15
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, false)); // row_bcast:31
-    return v;
-}
-
-constexpr int kTilesPerBlock = 4;
 #define GSR_LOG2E 1.4426950408889634f
 
 // Diagnostic builds (make trace -> libgsr_trace.so): every render wave stores (start, end,
@@ -684,10 +673,9 @@ __device__ inline void wave_lds_sync() {
 // Longest-processing-time-first dispatch order, computed by ONE block: order[] lists the T tiles
 // by descending cost(t) (bucketed into 2048 log-free linear buckets; arbitrary order inside a bucket,
 // which only affects scheduling).  `s_hist` must hold 2048 words, `s_red` 16.  All threads call it.
-struct IdentityPos { __device__ uint32_t operator()(uint32_t p) const { return p; } };
-template <typename CostFn, typename PosMap = IdentityPos>
+template <typename CostFn>
 __device__ inline void lpt_order(int T, CostFn cost, uint32_t *__restrict__ order, uint32_t *s_hist,
-                                 uint32_t *s_red, PosMap pos = PosMap()) {
+                                 uint32_t *s_red) {
     uint32_t mx = 0;
     for (int t = threadIdx.x; t < T; t += blockDim.x) mx = max(mx, cost(t));
     for (int d = 32; d > 0; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
@@ -713,71 +701,7 @@ __device__ inline void lpt_order(int T, CostFn cost, uint32_t *__restrict__ orde
     }
     __syncthreads();
     for (int t = threadIdx.x; t < T; t += blockDim.x)
-        order[pos(atomicAdd(&s_hist[kOrderBuckets - 1 - (cost(t) >> shift)], 1u))] = (uint32_t)t;
-}
-
-// The same LPT order when every thread already holds the costs of the c consecutive tiles
-// t = threadIdx.x * c + i (i < c <= C) in registers: the single-block scan kernels prefetch them with
-// every load in flight instead of re-reading global memory in dependent strided loops.
-template <int C, typename PosMap = IdentityPos>
-__device__ inline void lpt_order_regs(int T, int c, const uint32_t (&cost)[C], uint32_t *__restrict__ order,
-                                      uint32_t *s_hist, uint32_t *s_red, PosMap pos = PosMap()) {
-    const int t0 = threadIdx.x * c;
-    uint32_t mx = 0;
-#pragma unroll
-    for (int i = 0; i < C; ++i)
-        if (i < c && t0 + i < T) mx = max(mx, cost[i]);
-    for (int d = 32; d > 0; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = mx;
-    for (int b = threadIdx.x; b < kOrderBuckets; b += blockDim.x) s_hist[b] = 0;
-    __syncthreads();
-    mx = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) mx = max(mx, s_red[w]);
-    int shift = 0;
-    while ((mx >> shift) >= (uint32_t)kOrderBuckets) ++shift;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < C; ++i)
-        if (i < c && t0 + i < T) atomicAdd(&s_hist[kOrderBuckets - 1 - (cost[i] >> shift)], 1u);
-    __syncthreads();
-    uint32_t carry = 0;
-    for (int base = 0; base < kOrderBuckets; base += blockDim.x) {
-        const int b = base + threadIdx.x;
-        const uint32_t h = b < kOrderBuckets ? s_hist[b] : 0;
-        uint32_t tot;
-        const uint32_t ex = block_excl_scan_u32(h, s_red, &tot) + carry;
-        if (b < kOrderBuckets) s_hist[b] = ex;
-        carry += tot;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < C; ++i)
-        if (i < c && t0 + i < T)
-            order[pos(atomicAdd(&s_hist[kOrderBuckets - 1 - (cost[i] >> shift)], 1u))] = (uint32_t)(t0 + i);
-}
-// Boustrophedon over rounds of S slots: rank p of round r = p / S lands at slot p % S in even rounds and
-// at the mirrored slot in odd ones (the last, partial round mirrors within its own length).  For a
-// launch whose waves are all resident at once (one wave per SIMD per round, S = SIMDs), each SIMD
-// then holds one heavy and one light tile of every pair of rounds instead of the k-th heaviest of
-// every round.
-struct SnakePos {
-    uint32_t S, T;
-    __device__ uint32_t operator()(uint32_t p) const {
-        const uint32_t r = p / S, j = p - r * S;
-        if (!(r & 1u)) return p;
-        const uint32_t L = min(S, T - r * S);
-        return r * S + (L - 1u - j);
-    }
-};
-
-// Tiles per thread held in registers by the single-block kernels (1024 threads): T <= 16384.
-constexpr int kScanRegs = 16;
-
-// XCD-aware bijection over T tiles: blocks b, b+8, ... (one XCD under round-robin dispatch) take a
-// contiguous run of tiles, so neighbouring tiles share Gaussian records in one L2.  Speed only.
-__device__ inline int remap_tile(int b, int T) {
-    const int x = b & 7, i = b >> 3, q = T >> 3, r = T & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
+        order[atomicAdd(&s_hist[kOrderBuckets - 1 - (cost(t) >> shift)], 1u)] = (uint32_t)t;
 }
 
 // Conservative (tile, Gaussian) cull: true only if NO pixel centre of the pixel rectangle

@@ -366,11 +366,10 @@ __global__ __launch_bounds__(kColW * kColG) void k_bin_colscan(
 }
 
 // ------------------------------------------------------------------------------------------
-// Single block (1024 threads): exclusive scan of the T tile counts -> ranges/cursors, and of the
-// NB chunk sums -> chunk emission offsets.  meta[0] = K.  Up to 16384 tiles every thread holds its
-// (at most 16) consecutive counts in registers, loaded with every load in flight, so the kernel does
-// one block scan instead of a chain of dependent strided load-scan rounds; larger grids take the
-// strided path.
+// Global-atomic binning only (T > kMaxLdsTiles; smaller grids take k_bin_colscan).  Single block
+// (1024 threads): strided exclusive scans of the T tile counts -> ranges/cursors and segment offsets,
+// and of the NB chunk sums -> chunk emission offsets; then the list classes, meta[0] = K with the
+// host words, and the forward's dispatch order.
 __global__ __launch_bounds__(1024) void k_bin_scan(int T, int NB, const uint32_t *__restrict__ tile_count,
                                                    uint2 *__restrict__ ranges,
                                                    uint32_t *__restrict__ tile_cursor,
@@ -385,65 +384,6 @@ __global__ __launch_bounds__(1024) void k_bin_scan(int T, int NB, const uint32_t
     __shared__ uint32_t s_hist[kOrderBuckets];
     __shared__ uint32_t s_cls[3];
     if (threadIdx.x < 3) s_cls[threadIdx.x] = 0;
-    if (T <= kScanRegs * (int)blockDim.x && NB <= (int)blockDim.x) {
-        // fast path: thread owns tiles [tid c, tid c + c); all counts loaded up front, one block scan
-        const int c = div_up(T, (int)blockDim.x), t0 = threadIdx.x * c;
-        uint32_t cnt[kScanRegs];
-#pragma unroll
-        for (int i = 0; i < kScanRegs; ++i) cnt[i] = (i < c && t0 + i < T) ? tile_count[t0 + i] : 0u;
-        const uint32_t bsum = (int)threadIdx.x < NB ? block_sums[threadIdx.x] : 0u;
-        uint32_t mine = 0;
-#pragma unroll
-        for (int i = 0; i < kScanRegs; ++i) mine += cnt[i];
-        uint32_t K;
-        uint32_t ex = block_excl_scan_u32(mine, s_red, &K);
-#pragma unroll
-        for (int i = 0; i < kScanRegs; ++i) {
-            const int t = t0 + i;
-            if (i < c && t < T) {
-                ranges[t] = cnt[i] ? make_uint2(ex, ex + cnt[i]) : make_uint2(0, 0);  // empty: {0,0} like the reference
-                tile_cursor[t] = ex;
-                if (cnt[i] > (uint32_t)kSortCap) {  // long: merge-sorted; listed from the end
-                    sort_lists[T - 1 - atomicAdd(&s_cls[1], 1u)] = (uint32_t)t;
-                    atomicMax(&s_cls[2], cnt[i]);
-                } else if (cnt[i] > (uint32_t)kFwdSortCap) {
-                    sort_lists[atomicAdd(&s_cls[0], 1u)] = (uint32_t)t;
-                }
-            }
-            ex += cnt[i];
-        }
-        // backward segment boundaries: exclusive prefix over tiles (index of each tile's first state)
-        uint32_t nbs = 0;
-#pragma unroll
-        for (int i = 0; i < kScanRegs; ++i) nbs += (i < c && t0 + i < T) ? seg_bounds(cnt[i], ks) : 0u;
-        uint32_t nbt;
-        uint32_t sex = block_excl_scan_u32(nbs, s_red, &nbt);
-#pragma unroll
-        for (int i = 0; i < kScanRegs; ++i) {
-            if (i < c && t0 + i < T) {
-                seg_off[t0 + i] = sex;
-                sex += seg_bounds(cnt[i], ks);
-            }
-        }
-        if (threadIdx.x == 0) seg_off[T] = nbt;
-        uint32_t btot;
-        const uint32_t bex = block_excl_scan_u32(bsum, s_red, &btot);  // contains the barrier s_cls needs
-        if ((int)threadIdx.x < NB) block_off[threadIdx.x] = bex;
-        if (threadIdx.x == 0) {
-            meta[0] = K;
-            // speculative enqueue (gsr_forward_info): the kernels queued before the host read K run
-            // only when the BINNING capacity holds K and no list needs the merge sort
-            meta[1] = (cap && K <= cap && s_cls[1] == 0u) ? 1u : 0u;
-            meta[2] = s_cls[0];
-            if (host_words) {
-                for (int q = 0; q < 3; ++q)
-                    __hip_atomic_store(host_words + 1 + q, s_cls[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(host_words, K, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-        lpt_order_regs<kScanRegs>(T, c, cnt, tile_order, s_hist, s_red);
-        return;
-    }
     uint32_t carry = 0;
     for (int base = 0; base < T; base += blockDim.x) {
         const int t = base + threadIdx.x;
@@ -505,9 +445,10 @@ __global__ __launch_bounds__(1024) void k_bin_scan(int T, int NB, const uint32_t
 }
 
 // ------------------------------------------------------------------------------------------
-// Scatter keys into tile buckets.  Each chunk re-counts its tile histogram in LDS, reserves one
-// contiguous slab per non-empty tile with a single global atomic, then hands out slots from LDS.
-// The order inside a tile is arbitrary here; k_tile_sort makes it canonical.
+// Scatter keys into tile buckets.  USE_LDS: each chunk loads its row of the column scan
+// (k_bin_colscan: its slab's start inside every tile) on top of the tile's range start, then hands
+// out slots from LDS; otherwise slots come from the tiles' global cursors.  The order inside a tile
+// is arbitrary here; the sorts make it canonical.
 template <bool USE_LDS>
 __global__ __launch_bounds__(kBinThreads) void k_bin_emit(int P, int CH, int T, int gx,
                                                   const uint2 *__restrict__ rects,
@@ -1338,16 +1279,16 @@ __global__ void k_mark_visible(int P, const float *__restrict__ means3D,
 // ==========================================================================================
 template <int MC>
 static void preprocess_mc(const FwdArgs &a, hipStream_t s) {
-    k_preprocess<MC><<<div_up(a.P, kShBlock), kShBlock, sizeof(float) * kShBlock * (MC ? sh_row_stride(MC) : 0), s>>>(
-        a.P, a.D, a.M, a.means3D, a.scales, a.scale_modifier, a.rotations, a.opacities, a.shs,
-        a.colors_precomp, a.cov3D_precomp, a.viewmatrix, a.projmatrix, a.campos, a.W, a.H, a.tan_fovx,
-        a.tan_fovy, a.focal_x, a.focal_y, a.gx, a.gy, a.radii, a.depth, a.rec, a.rect, a.tiles, a.act, a.cs,
-        a.tile_count, a.gx * a.gy, a.clampm);
+    k_preprocess<MC><<<div_up(a.v.P, kShBlock), kShBlock, sizeof(float) * kShBlock * (MC ? sh_row_stride(MC) : 0), s>>>(
+        a.v.P, a.v.D, a.v.M, a.v.means3D, a.v.scales, a.v.scale_modifier, a.v.rotations, a.v.opacities, a.v.shs,
+        a.v.colors_precomp, a.v.cov3D_precomp, a.v.viewmatrix, a.v.projmatrix, a.v.campos, a.v.W, a.v.H, a.v.tan_fovx,
+        a.v.tan_fovy, a.v.focal_x, a.v.focal_y, a.v.gx, a.v.gy, a.radii, a.depth, a.rec, a.rect, a.tiles, a.v.act, a.v.cs,
+        a.tile_count, a.v.gx * a.v.gy, a.clampm);
 }
 
 hipError_t launch_preprocess(const FwdArgs &a, hipStream_t s) {
-    if (a.P == 0) return hipSuccess;
-    const int mc = a.shs ? a.M : 0;
+    if (a.v.P == 0) return hipSuccess;
+    const int mc = a.v.shs ? a.v.M : 0;
     switch (mc) {
         case 16: preprocess_mc<16>(a, s); break;
         case 9: preprocess_mc<9>(a, s); break;
@@ -1359,42 +1300,43 @@ hipError_t launch_preprocess(const FwdArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_bin_count(const FwdArgs &a, hipStream_t s) {
-    const BinGrid bg(a.P);
-    const int T = a.gx * a.gy;
+    const BinGrid bg(a.v.P);
+    const int T = a.v.gx * a.v.gy;
     if (bg.NB == 0) return hipSuccess;  // (tile_count was zeroed by k_preprocess)
     if (T <= kMaxLdsTiles)
-        k_bin_count<true><<<bg.NB, kBinThreads, sizeof(uint32_t) * T, s>>>(a.P, bg.CH, T, a.gx, a.rect, a.tiles, a.tile_count, a.block_sums, a.chunk_off, a.items_ws, a.scan_ws);
+        k_bin_count<true><<<bg.NB, kBinThreads, sizeof(uint32_t) * T, s>>>(a.v.P, bg.CH, T, a.v.gx, a.rect, a.tiles, a.tile_count, a.block_sums, a.chunk_off, a.items_ws, a.scan_ws);
     else
-        k_bin_count<false><<<bg.NB, kBinThreads, 0, s>>>(a.P, bg.CH, T, a.gx, a.rect, a.tiles, a.tile_count, a.block_sums, nullptr, a.items_ws, nullptr);
+        k_bin_count<false><<<bg.NB, kBinThreads, 0, s>>>(a.v.P, bg.CH, T, a.v.gx, a.rect, a.tiles, a.tile_count, a.block_sums, nullptr, a.items_ws, nullptr);
     return hipGetLastError();
 }
 
 // LDS binning (T <= kMaxLdsTiles): the column scan with the single-pass tile scan; otherwise the
-// one-block scan over the globally counted tiles
+// one-block scan over the globally counted tiles.  k_bin_scan serves only T > kMaxLdsTiles: NB == 0
+// means P == 0, and the forward returns before any launch then.
 hipError_t launch_bin_scan(const FwdArgs &a, uint32_t *host_words, hipStream_t s) {
-    const BinGrid bg(a.P);
-    const int T = a.gx * a.gy;
+    const BinGrid bg(a.v.P);
+    const int T = a.v.gx * a.v.gy;
     if (T <= kMaxLdsTiles && bg.NB > 0)
         k_bin_colscan<<<div_up(T, kColW), kColW * kColG, 0, s>>>(T, bg.NB, a.chunk_off, a.tile_count, a.ranges,
                                                                 a.tile_cursor, a.seg_off, a.sort_lists, a.tile_rank,
                                                                 a.scan_ws, a.block_sums, a.block_off, a.meta,
-                                                                host_words, a.spec_cap, seg_log2(a.P));
+                                                                host_words, a.spec_cap, seg_log2(a.v.P));
     else
         k_bin_scan<<<1, 1024, 0, s>>>(T, bg.NB, a.tile_count, a.ranges, a.tile_cursor,
                                       a.block_sums, a.block_off, a.meta, host_words, a.tile_order_f,
-                                      a.sort_lists, a.seg_off, a.spec_cap, seg_log2(a.P));
+                                      a.sort_lists, a.seg_off, a.spec_cap, seg_log2(a.v.P));
     return hipGetLastError();
 }
 
 hipError_t launch_bin_emit(const FwdArgs &a, int K, hipStream_t s) {
-    const BinGrid bg(a.P);
-    const int T = a.gx * a.gy;
+    const BinGrid bg(a.v.P);
+    const int T = a.v.gx * a.v.gy;
     if (bg.NB == 0) return hipSuccess;
     if (T <= kMaxLdsTiles)
-        k_bin_emit<true><<<bg.NB, kBinThreads, sizeof(uint32_t) * T, s>>>(a.P, bg.CH, T, a.gx, a.rect, a.tiles, a.depth, a.block_off, a.tile_cursor, a.goff, a.pairs, (uint32_t)K, a.chunk_off, a.spec_ok,
+        k_bin_emit<true><<<bg.NB, kBinThreads, sizeof(uint32_t) * T, s>>>(a.v.P, bg.CH, T, a.v.gx, a.rect, a.tiles, a.depth, a.block_off, a.tile_cursor, a.goff, a.pairs, (uint32_t)K, a.chunk_off, a.spec_ok,
                                                                            a.tile_count, a.tile_rank, a.scan_ws + 2 * kScanBlocksMax + kScanCtr, a.tile_order_f);
     else
-        k_bin_emit<false><<<bg.NB, kBinThreads, 0, s>>>(a.P, bg.CH, T, a.gx, a.rect, a.tiles, a.depth, a.block_off, a.tile_cursor, a.goff, a.pairs, (uint32_t)K, a.chunk_off, a.spec_ok,
+        k_bin_emit<false><<<bg.NB, kBinThreads, 0, s>>>(a.v.P, bg.CH, T, a.v.gx, a.rect, a.tiles, a.depth, a.block_off, a.tile_cursor, a.goff, a.pairs, (uint32_t)K, a.chunk_off, a.spec_ok,
                                                         nullptr, nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
@@ -1403,14 +1345,14 @@ hipError_t launch_tile_sort(const FwdArgs &a, uint32_t n_mid, uint32_t n_vlong, 
                             hipStream_t s) {
     // lists of up to kFwdSortCap pairs are sorted inside k_render_fwd; up to kSortCap by one block
     // per tile; longer ones by chunk sorts + merge passes
-    const int T = a.gx * a.gy;
+    const int T = a.v.gx * a.v.gy;
     if (a.spec_ok) {  // speculative: the count is on the device; blocks loop over it (none here: n_vlong == 0)
         const int nb = a.spec_sort_blocks ? (int)a.spec_sort_blocks : kSpecSortBlocks;
-        k_tile_sort<<<std::min(T, nb), 512, 0, s>>>(a.gx, a.sort_lists, a.ranges, a.pairs, a.point_list,
+        k_tile_sort<<<std::min(T, nb), 512, 0, s>>>(a.v.gx, a.sort_lists, a.ranges, a.pairs, a.point_list,
                                                                  a.slot_emit, 0u, a.spec_ok);
         return hipGetLastError();
     }
-    if (n_mid) k_tile_sort<<<n_mid, 512, 0, s>>>(a.gx, a.sort_lists, a.ranges, a.pairs, a.point_list, a.slot_emit,
+    if (n_mid) k_tile_sort<<<n_mid, 512, 0, s>>>(a.v.gx, a.sort_lists, a.ranges, a.pairs, a.point_list, a.slot_emit,
                                                  n_mid, nullptr);
     if (n_vlong) {
         const dim3 grid((unsigned)div_up((int)max_n, kSortCap), n_vlong);
@@ -1430,18 +1372,18 @@ hipError_t launch_tile_sort(const FwdArgs &a, uint32_t n_mid, uint32_t n_vlong, 
 }
 
 hipError_t launch_render_fwd(const FwdArgs &a, hipStream_t s) {
-    const int T = a.gx * a.gy;
+    const int T = a.v.gx * a.v.gy;
     auto k = a.exact ? k_render_fwd<true> : k_render_fwd<false>;
-    k<<<T, 256, 0, s>>>(a.W, a.H, a.gx, T, a.tile_order_f, a.ranges, a.pairs,
-                        a.point_list, a.slot_emit, a.rec, a.bg, a.out_color, a.out_depth, a.pix_end, a.n_contrib,
-                        a.tile_maxc, a.seg_off, a.seg_state, a.spec_ok, seg_log2(a.P), a.gate, a.gate_seq,
+    k<<<T, 256, 0, s>>>(a.v.W, a.v.H, a.v.gx, T, a.tile_order_f, a.ranges, a.pairs,
+                        a.point_list, a.slot_emit, a.rec, a.v.bg, a.out_color, a.out_depth, a.pix_end, a.n_contrib,
+                        a.tile_maxc, a.seg_off, a.seg_state, a.spec_ok, seg_log2(a.v.P), a.gate, a.gate_seq,
                         a.gate_err, a.gate_timeout, a.tile_flag, a.near_rec, a.items_ws + kTSatCtr, a.tsat_list,
-                        tsat_capacity(a.W * a.H));
+                        tsat_capacity(a.v.W * a.v.H));
     if (a.exact)  // the flagged pixels' exact re-walk (a fixed grid that loops over the device-side count)
-        k_render_tsat<<<kTSatBlocks, kTSatThreads, 0, s>>>(a.W, a.H, a.point_list, a.rec, a.bg, a.out_color, a.out_depth,
+        k_render_tsat<<<kTSatBlocks, kTSatThreads, 0, s>>>(a.v.W, a.v.H, a.point_list, a.rec, a.v.bg, a.out_color, a.out_depth,
                                                  a.pix_end, a.n_contrib, a.seg_off, a.seg_state, a.items_ws + kTSatCtr,
-                                                 a.tsat_list, tsat_capacity(a.W * a.H), a.spec_ok, seg_log2(a.P),
-                                                 a.gx);
+                                                 a.tsat_list, tsat_capacity(a.v.W * a.v.H), a.spec_ok, seg_log2(a.v.P),
+                                                 a.v.gx);
     return hipGetLastError();
 }
 

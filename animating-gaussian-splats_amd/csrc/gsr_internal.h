@@ -5,13 +5,18 @@
 
 namespace gsr {
 
-struct FwdArgs {
-    // inputs
+// One view's inputs, shared by the forward's and the backward's argument bundles: the frame and its
+// tile grid, the camera, and the Gaussians' parameter arrays (opacities: the forward only).
+struct ViewIn {
     int P, D, M, W, H, gx, gy, act;
     float scale_modifier, tan_fovx, tan_fovy, focal_x, focal_y;
     const float *means3D, *scales, *rotations, *opacities, *shs, *colors_precomp, *cov3D_precomp;
     const float *viewmatrix, *projmatrix, *campos, *bg;
     CamStrides cs;
+};
+
+struct FwdArgs {
+    ViewIn v;
     // geom
     float *depth; float4 *rec; uint2 *rect; uint32_t *tiles; uint32_t *goff; uint8_t *clampm;
     // image
@@ -46,11 +51,8 @@ struct FwdArgs {
 constexpr int kSpecSortBlocks = 512;
 
 struct BwdArgs {
-    int P, D, M, W, H, gx, gy, K, act;
-    float scale_modifier, tan_fovx, tan_fovy, focal_x, focal_y;
-    const float *means3D, *scales, *rotations, *shs, *colors_precomp, *cov3D_precomp;
-    const float *viewmatrix, *projmatrix, *campos, *bg;
-    CamStrides cs;
+    ViewIn v;
+    int K;
     const int *radii;
     // saved state
     const float4 *rec; const uint2 *rect; const uint8_t *clampm;

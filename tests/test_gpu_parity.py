@@ -282,6 +282,36 @@ def test_wide_frame_global_binning(cuda):
     check_backward(_gpu_backward(a, rs, cuda, fw, dl), O.backward(st, dl.numpy()), 30_000, 0)
 
 
+def test_wide_frame_long_lists(cuda):
+    """The same frame with two clusters (built as in test_long_tile_lists) on top of the background
+    cloud, so k_bin_scan -- the scan of the global-atomic binning path -- also classifies lists for
+    k_tile_sort (1024 < n <= 4096) and for the chunk sorts + merge passes (n > 4096).  Oracle:
+    K = 193307, one list of 2561 entries, and lists of 5491, 5525 and 9234 entries (three chunks, two
+    merge passes)."""
+    W, H = 4224, 1040
+    a, rs = _inputs(30_000, W, H, 1100.0, 0.01, seed=8)
+    g = torch.Generator().manual_seed(4)
+    for n, cx in ((2_500, 0.03), (14_000, 0.03 + 256 / 1100)):
+        m = torch.zeros(n, 3)
+        m[:, 0] = cx + torch.rand(n, generator=g) * 0.01 - 0.005
+        m[:, 1] = torch.rand(n, generator=g) * 0.01 - 0.005
+        m[:, 2] = torch.rand(n, generator=g) * 2 - 1
+        c = {"means3D": m, "colors_precomp": torch.rand(n, 3, generator=g),
+             "opacities": torch.full((n, 1), 0.05), "scales": torch.full((n, 3), 0.004),
+             "rotations": torch.tensor([[1.0, 0, 0, 0]]).repeat(n, 1)}
+        for k, v in c.items():
+            a[k] = torch.cat([a[k], v], 0)
+    P = a["means3D"].shape[0]
+    st = _ora_forward(a, rs)
+    n = np.diff(st["ranges"].astype(np.int64), axis=1)[:, 0]
+    assert ((n > 1024) & (n <= 4096)).sum() >= 1 and (n > 4096).sum() >= 1
+    assert n.max() > 2 * 4096  # more than two chunks: a second merge pass
+    fw = _gpu_forward(a, rs, cuda)
+    check_forward(fw, st)
+    dl = S.upstream_grad(H, W, device="cpu")
+    check_backward(_gpu_backward(a, rs, cuda, fw, dl), O.backward(st, dl.numpy()), P, 0)
+
+
 def test_empty_and_all_culled(cuda):
     rs = S.render_settings(48, 32, S.intrinsics(48.0, 48, 32), S.look_at(0, 0, 4), device="cpu")
     rs = rs._replace(bg=torch.tensor([0.25, 0.5, 0.75]))

@@ -31,6 +31,13 @@ __device__ inline void row_halves3(float &X, float &Y, float &Z) {
 '''
 
 
+def makefile_sources(csrc: str) -> list[str]:
+    """The library's translation units: the SRCS line of csrc/Makefile, the one list of them."""
+    m = re.search(r"^SRCS\s*=\s*(.+)$", open(os.path.join(csrc, "Makefile")).read(), re.M)
+    assert m, "SRCS not found in csrc/Makefile"
+    return m.group(1).split()
+
+
 def make_variant(out: str, form: str = "seq", sources=None, csrc: str | None = None) -> None:
     csrc = csrc or os.path.join(REPO, "animating-gaussian-splats_amd", "csrc")
     with tempfile.TemporaryDirectory() as td:
@@ -52,8 +59,7 @@ def make_variant(out: str, form: str = "seq", sources=None, csrc: str | None = N
             assert t.count('asm("s_nop 1\\n\\t"') == 1, "row_halves3's s_nop not found"
             t = t.replace('asm("s_nop 1\\n\\t"', 'asm(')
         open(p, "w").write(t)
-        srcs = sources or ["gsr_api.hip", "gsr_forward.hip", "gsr_backward.hip", "gsr_loss.hip", "gsr_densify.hip",
-                           "gsr_adam.hip", "gsr_io.hip"]
+        srcs = sources or makefile_sources(src)
         subprocess.run([HIPCC, *FLAGS, "-shared", "-o", os.path.abspath(out), *srcs], cwd=src, check=True,
                        capture_output=True)
 
