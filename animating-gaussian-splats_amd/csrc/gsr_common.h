@@ -135,7 +135,8 @@ constexpr int kItemsWsWords = 2 * kOrderBuckets + 64;
 // k_bin_count; the item kernels use words [0, 2 kOrderBuckets])
 constexpr int kTSatCtr = 2 * kOrderBuckets + 8;
 // records of the pixels the exact saturation re-walk redoes (32 B each, IMAGE tsat_list): one per 8 pixels
-// (measured ~0.1 % of a C3 view's pixels; past the capacity a pixel keeps the fast walk's outputs)
+// (measured ~0.1 % of a C3 view's pixels; with more flagged pixels than records k_render_tsat leaves the list
+// and finds them by scanning the per-pixel state instead, so the count may exceed the capacity)
 __host__ __device__ constexpr uint32_t tsat_capacity(int npix) { return (uint32_t)(npix / 8 + 64); }
 
 // The single-pass tile scan of k_bin_colscan (IMAGE.scan_ws, zeroed by k_bin_count): one look-back

@@ -835,6 +835,9 @@ __device__ inline void gate_wait(const uint32_t *gate, uint32_t seq, uint32_t *e
 #define GSR_TSAT_THREADS 64
 #endif
 constexpr int kTSatThreads = GSR_TSAT_THREADS;  // threads (list entries per round) of a re-walk block
+// the pixels the re-walk redoes: final T (after `last` list entries) below the upper end of the drift window.
+// k_render_fwd flags with it and k_render_tsat's overflow scan finds the same pixels again from (pix_end.w, n_contrib)
+__device__ inline bool tsat_flagged(float T, uint32_t last) { return T < kTSat * (1.0f + t_window(last)); }
 struct TSatRec { float4 r0, r1, r3; };  // position + pre-scaled conic, (C2, opacity, ...), exact conic
 __device__ inline TSatRec tsat_load(const float4 *__restrict__ rec, uint32_t g, bool v) {
     TSatRec t;
@@ -1152,7 +1155,7 @@ __global__ __launch_bounds__(256) GSR_FWD_ATTR void k_render_fwd(
     // EXACT: a pixel whose final T lies within the drift window of 1e-4 (gsr_common.h t_window) is redone by
     // k_render_tsat with the reference's transmittance test; its record carries what that needs
     // (pixel, list start and length, fast n_contrib, fast colour + depth), so the re-walk starts with one load
-    if (EXACT && inside && Tt < kTSat * (1.0f + t_window(last))) {
+    if (EXACT && inside && tsat_flagged(Tt, last)) {
         const uint32_t slot = atomicAdd(tsat_n, 1u);
         if (slot < tsat_cap) {
             uint4 *r = reinterpret_cast<uint4 *>(tsat_list) + 2 * (size_t)slot;
@@ -1192,7 +1195,9 @@ __global__ __launch_bounds__(256) GSR_FWD_ATTR void k_render_fwd(
 // The exact saturation re-walk of the pixels k_render_fwd flagged: one kTSatThreads-thread block per pixel, all in
 // parallel (a fixed grid looping over the device-side count), the walk of tsat_chain / tsat_store above.
 // Each pixel's record (written by k_render_fwd) holds its position, list and fast state, so a block starts
-// with one load.  (A version that re-walked inside k_render_fwd's blocks, after their blend, was slower:
+// with one load.  With more flagged pixels than the list holds (the count goes on past the capacity) the
+// blocks find the flagged pixels by scanning the per-pixel state instead, so the result is exact for any
+// count.  (A version that re-walked inside k_render_fwd's blocks, after their blend, was slower:
 // the tiles with the most flagged pixels are the long ones at the head of the LPT order)
 #ifndef GSR_TSAT_BLOCKS
 #define GSR_TSAT_BLOCKS 4096
@@ -1203,12 +1208,13 @@ __global__ __launch_bounds__(kTSatThreads) void k_render_tsat(
     const float *__restrict__ bg, float *__restrict__ out_color, float *__restrict__ out_depth,
     float4 *__restrict__ pix_end, uint32_t *__restrict__ n_contrib, const uint32_t *__restrict__ seg_off,
     float4 *__restrict__ seg_state, const uint32_t *__restrict__ tsat_n, const uint32_t *__restrict__ tsat_list,
-    uint32_t tsat_cap, const uint32_t *__restrict__ spec_ok, int ks, int gx) {
+    uint32_t tsat_cap, const uint32_t *__restrict__ spec_ok, int ks, int gx, const uint2 *__restrict__ ranges) {
     constexpr int NT = kTSatThreads;
     __shared__ float4 s_buf[(3 * NT + 4 + 3) / 4];  // the round's contributors: 1 - alpha (+ padding), alpha, position
     __shared__ uint32_t s_rc[4];   // contributors per wave
     if (spec_ok && *spec_ok == 0u) return;  // speculative launch whose capacity failed: redone by the host
-    const uint32_t cnt = min(*tsat_n, tsat_cap);
+    const uint32_t flagged = *tsat_n;
+    const uint32_t cnt = flagged > tsat_cap ? 0u : flagged;  // (past the capacity: the scan below instead)
 #ifdef GSR_TRACE
     const uint64_t tr_b = __builtin_amdgcn_s_memrealtime();  // (diagnostic) the block's start
 #endif
@@ -1255,6 +1261,46 @@ __global__ __launch_bounds__(kTSatThreads) void k_render_tsat(
             o[3] = (tr_c - tr_i) | ((tr_i - tr_b) << 32);
         }
 #endif
+    }
+    if (__builtin_expect(flagged > tsat_cap, 0)) {
+        // More flagged pixels than records (opaque surfaces seen from close: whole images): the list is
+        // incomplete, so it is not used at all.  What a record holds is still in the pixel's own state --
+        // pix_end (fast colour, T), out_depth, n_contrib, the tile's range -- and no pixel has been redone
+        // yet, so k_render_fwd's flag test on (pix_end.w, n_contrib) finds exactly the flagged pixels.  The
+        // blocks scan the image 64 pixels at a time (every wave tests the same 64, so the mask of flagged ones
+        // is block-uniform without LDS: the kernel's LDS footprint is the common path's) and re-walk the flagged
+        // ones; every pixel belongs to one block, which reads its state before writing it.  Decided on the
+        // device: no host read, no launch.
+        const uint32_t npix = (uint32_t)W * (uint32_t)H;
+        for (uint32_t base = blockIdx.x * 64u; base < npix; base += gridDim.x * 64u) {
+            const uint32_t p = base + (threadIdx.x & 63u);
+            uint64_t fm = __ballot(p < npix && tsat_flagged(pix_end[p].w, n_contrib[p]));
+            __syncthreads();  // every wave has read the chunk's state before a pixel of it is rewritten
+            while (fm) {
+                const uint32_t pid = base + (uint32_t)__builtin_ctzll(fm);
+                fm &= fm - 1;
+                const int px = (int)(pid % (uint32_t)W), py = (int)(pid / (uint32_t)W);
+                const int tile = (py / kTileH) * gx + px / kTileW;
+                const uint2 rg = ranges[tile];
+                const float4 pe = pix_end[pid];
+                const int nf = (int)n_contrib[pid];
+                const float dfast = out_depth[pid];
+                float T = 1.0f;
+                uint32_t nex = 0;
+                float4 E = make_float4(0.f, 0.f, 0.f, 0.f);
+                tsat_chain(nf, point_list + rg.x, (float)px, (float)py, rec, s_rc, s_q, s_a, s_pos, T, nex, E);
+                if (threadIdx.x == 0) {  // wave 0 holds the result: broadcast through LDS
+                    s_rc[0] = nex;
+                    s_rc[1] = __float_as_uint(T);
+                    s_q[0] = E.x; s_q[1] = E.y; s_q[2] = E.z; s_q[3] = E.w;
+                }
+                __syncthreads();
+                tsat_store(px, py, W, H, (int)(rg.y - rg.x), make_float4(pe.x, pe.y, pe.z, 0.f), dfast,
+                           __uint_as_float(s_rc[1]), s_rc[0], make_float4(s_q[0], s_q[1], s_q[2], s_q[3]), bg,
+                           out_color, out_depth, pix_end, n_contrib, seg_off[tile], seg_state, ks, nullptr);
+                __syncthreads();  // (the LDS is reused by the next pixel)
+            }
+        }
     }
 }
 
@@ -1383,7 +1429,7 @@ hipError_t launch_render_fwd(const FwdArgs &a, hipStream_t s) {
         k_render_tsat<<<kTSatBlocks, kTSatThreads, 0, s>>>(a.v.W, a.v.H, a.point_list, a.rec, a.v.bg, a.out_color, a.out_depth,
                                                  a.pix_end, a.n_contrib, a.seg_off, a.seg_state, a.items_ws + kTSatCtr,
                                                  a.tsat_list, tsat_capacity(a.v.W * a.v.H), a.spec_ok, seg_log2(a.v.P),
-                                                 a.v.gx);
+                                                 a.v.gx, a.ranges);
     return hipGetLastError();
 }
 

@@ -11,6 +11,9 @@ oracle's forward state; the reference's gradient quirks are emulated explicitly:
 * the alpha gradient ignores the ``min(0.99, .)`` clamp (straight-through on the clamp),
 * ``means2D`` receives dL/d(pixel xy) scaled by (W/2, H/2), i.e. NDC units,
 * quaternions enter Sigma3D unnormalised (no normalisation derivative),
+* a view-space t.x / t.y clamped to the 1.3 tan(fov) frustum enters the Jacobian J as a constant
+  (dL/dt.x is zeroed and dL/dt.z does not see it), where autograd would differentiate clamp(x/z) z,
+* dL/dscale is not multiplied by ``scale_modifier`` (the scales enter as s + ((mod - 1) s).detach()),
 * the depth image carries no gradient.
 
 ``threshold_margin`` reports how far every evaluated (pixel, Gaussian) pair sits from the
@@ -90,14 +93,21 @@ def dense_forward(st, means3D, opacities, colors=None, shs=None, scales=None, ro
     xy = torch.stack([((ndc[:, 0] + 1.0) * W - 1.0) * 0.5, ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5], -1)
     xy.retain_grad()
     if cov3D is None:
-        cov3D = cov3d_from(scales, rotations, st["scale_modifier"])
+        # scale-modifier rule: dL/dscale is not multiplied by the modifier (the modifier's share of the
+        # scale enters as a constant); the rotation gradient sees the modified scale
+        mod = st["scale_modifier"]
+        cov3D = cov3d_from(scales + ((mod - 1.0) * scales).detach(), rotations, 1.0)
     cov3D.retain_grad()
     fx = np.float32(W) / (np.float32(2.0) * np.float32(st["tanfovx"]))
     fy = np.float32(H) / (np.float32(2.0) * np.float32(st["tanfovy"]))
     limx, limy = 1.3 * st["tanfovx"], 1.3 * st["tanfovy"]
     tz = p_view[:, 2]
-    tx = torch.clamp(p_view[:, 0] / tz, -limx, limx) * tz
-    ty = torch.clamp(p_view[:, 1] / tz, -limy, limy) * tz
+    # frustum-clamp rule: a clamped t.x (t.y) is a constant in J -- no gradient to t.x, none to t.z through it
+    rx, ry = p_view[:, 0] / tz, p_view[:, 1] / tz
+    tx = torch.clamp(rx, -limx, limx) * tz
+    ty = torch.clamp(ry, -limy, limy) * tz
+    tx = torch.where((rx < -limx) | (rx > limx), tx.detach(), tx)
+    ty = torch.where((ry < -limy) | (ry > limy), ty.detach(), ty)
     zero = torch.zeros_like(tz)
     J = torch.stack([torch.stack([fx / tz, zero, -fx * tx / tz ** 2], -1),
                      torch.stack([zero, fy / tz, -fy * ty / tz ** 2], -1)], -2)  # (P,2,3)

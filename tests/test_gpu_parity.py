@@ -38,7 +38,8 @@ STATS = []
 
 
 def _inputs(P, W, H, focal, s0, seed=0, sh_degree=-1, yaw=0.0, height=0.0, distance=4.0,
-            bg=(0.0, 0.0, 0.0), active_degree=None, extra_coeffs=0, opacity_boost=0.0):
+            bg=(0.0, 0.0, 0.0), active_degree=None, extra_coeffs=0, opacity_boost=0.0, scale_modifier=1.0,
+            intr=None):
     p = S.synthetic_cloud(P, s0, sh_degree=sh_degree, seed=seed, device="cpu")
     a = {k: (v.detach() if isinstance(v, torch.Tensor) else v)
          for k, v in S.activated_inputs(p, sh_degree).items()}
@@ -48,9 +49,13 @@ def _inputs(P, W, H, focal, s0, seed=0, sh_degree=-1, yaw=0.0, height=0.0, dista
         g = torch.Generator().manual_seed(seed + 99)
         a["shs"] = torch.cat([a["shs"], 0.05 * torch.randn(P, extra_coeffs, 3, generator=g)], 1).contiguous()
     deg = max(sh_degree, 0) if active_degree is None else active_degree
-    rs = S.render_settings(W, H, S.intrinsics(focal, W, H), S.look_at(yaw, height, distance),
-                           device="cpu", sh_degree=deg)
-    rs = rs._replace(bg=torch.tensor(bg, dtype=torch.float32))
+    K = S.intrinsics(focal, W, H)
+    if intr is not None:  # (fy / fx, principal point offset from the centre in pixels): a custom K
+        K[1, 1] *= intr[0]
+        K[0, 2] += intr[1]
+        K[1, 2] += intr[2]
+    rs = S.render_settings(W, H, K, S.look_at(yaw, height, distance), device="cpu", sh_degree=deg)
+    rs = rs._replace(bg=torch.tensor(bg, dtype=torch.float32), scale_modifier=scale_modifier)
     return a, rs
 
 
@@ -183,19 +188,46 @@ CASES = {
     # ~2/3 of the opacities above 0.99: the backward's clamping walk (alpha = min(0.99, o G)) beside
     # batches without such pairs
     "opaque": (10_000, 256, 256, 256.0, 0.02, -1, dict(opacity_boost=5.0)),
+    # The camera inside the cloud (INSIDE, asserted by inside_regime): Gaussians behind the near cull at view
+    # depth 0.2 and right in front of it, view-space positions outside the 1.3 tan(fov) frustum (the clamped
+    # t.x / t.y of the projection Jacobian and the backward's keep_tx / keep_ty), rects clamped to the whole
+    # tile grid; scale modifiers other than 1, SH view directions of points next to the camera, and a K with
+    # fx != fy and an off-centre principal point (both enter projmatrix, not tanfov)
+    "inside": (3_000, 96, 80, 80.0, 0.05, -1, dict(yaw=20.0, height=0.1, distance=0.6)),
+    "inside_mod17": (3_000, 96, 80, 80.0, 0.05, -1, dict(yaw=20.0, height=0.1, distance=0.6, scale_modifier=1.7)),
+    "inside_sh3": (3_000, 96, 80, 80.0, 0.05, 3, dict(yaw=20.0, height=0.1, distance=0.6)),
+    # (seed 13: with modifier 0.6 no distance gives seed 3 a radius above the image width; oracle: 420 culled,
+    # 11 clamped with a gradient, radius 105, smallest visible depth 0.2006)
+    "skewed_k": (3_000, 96, 80, 80.0, 0.05, -1, dict(seed=13, yaw=20.0, height=0.1, distance=1.0, scale_modifier=0.6,
+                                                     intr=(1.3, 5.0, -3.0))),
 }
+INSIDE = ("inside", "inside_mod17", "inside_sh3", "skewed_k")
+
+
+def inside_regime(st, gref):
+    """(near-culled Gaussians, visible frustum-clamped Gaussians with a nonzero means3D gradient, largest
+    radius) of an oracle state and its backward."""
+    vm = st["vm"].astype(np.float64).reshape(4, 4)  # p_view = [p, 1] @ vm
+    pv = np.concatenate([st["means3D"].astype(np.float64), np.ones((st["P"], 1))], 1) @ vm
+    clamped = ((np.abs(pv[:, 0] / pv[:, 2]) > 1.3 * st["tanfovx"]) |
+               (np.abs(pv[:, 1] / pv[:, 2]) > 1.3 * st["tanfovy"]))
+    live = (st["radii"] > 0) & clamped & np.any(gref["means3D"] != 0, axis=1)
+    return int((pv[:, 2] <= 0.2).sum()), int(live.sum()), int(st["radii"].max())
 
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_forward_backward_parity(case, cuda):
     P, W, H, f, s0, shd, extra = CASES[case]
-    a, rs = _inputs(P, W, H, f, s0, seed=3, sh_degree=shd, **extra)
+    a, rs = _inputs(P, W, H, f, s0, sh_degree=shd, **{"seed": 3, **extra})
     st = _ora_forward(a, rs)
+    dl = S.upstream_grad(H, W, device="cpu")
+    gref = O.backward(st, dl.numpy())
+    if case in INSIDE:  # the case reaches the regime it is there for
+        culled, clamped, rmax = inside_regime(st, gref)
+        assert culled >= 1 and clamped >= 10 and rmax > max(W, H), (culled, clamped, rmax)
     fw = _gpu_forward(a, rs, cuda)
     pix, grad = allow(case)
     check_forward(fw, st, pix)
-    dl = S.upstream_grad(H, W, device="cpu")
-    gref = O.backward(st, dl.numpy())
     gb = _gpu_backward(a, rs, cuda, fw, dl)
     check_backward(gb, gref, P, st["M"], grad)
 
@@ -504,7 +536,7 @@ def fast_mode():
 def _case_inputs(case):
     if case in CASES:
         P, W, H, f, s0, shd, extra = CASES[case]
-        a, rs = _inputs(P, W, H, f, s0, seed=3, sh_degree=shd, **extra)
+        a, rs = _inputs(P, W, H, f, s0, sh_degree=shd, **{"seed": 3, **extra})
         return a, rs, P, W, H
     name, yaw, hgt = BASELINE_VIEWS[case]
     cfg, a = _baseline_cloud(name)

@@ -73,11 +73,13 @@ def test_empty_and_culled():
     np.testing.assert_array_equal(st["color"], np.broadcast_to(bg[:, None, None], (3, H, W)))
 
 
-def _autograd_case(seed, sh_degree=-1, use_cov3D=False, bg=(0.0, 0.0, 0.0), W=48, H=40, P=40):
+def _autograd_case(seed, sh_degree=-1, use_cov3D=False, bg=(0.0, 0.0, 0.0), W=48, H=40, P=40, yaw=0.0,
+                   height=0.0, distance=4.0, scale_modifier=1.0):
     """Returns (oracle grads, autograd grads) on a scene whose decisions are well away from thresholds."""
     for s in range(seed, seed + 40):
-        p, a, rs = _scene(P, W, H, 48.0, 0.06, seed=s, sh_degree=sh_degree)
-        rs = rs._replace(bg=torch.tensor(bg, dtype=torch.float32))
+        p, a, rs = _scene(P, W, H, 48.0, 0.06, seed=s, sh_degree=sh_degree, yaw=yaw, height=height,
+                          distance=distance)
+        rs = rs._replace(bg=torch.tensor(bg, dtype=torch.float32), scale_modifier=scale_modifier)
         cov = None
         if use_cov3D:
             cov = DT.cov3d_from(a["scales"].double(), a["rotations"].double(), 1.0).float().numpy()
@@ -108,8 +110,17 @@ def _autograd_case(seed, sh_degree=-1, use_cov3D=False, bg=(0.0, 0.0, 0.0), W=48
             ref["scales"], ref["rotations"] = leaf["scales"].grad, leaf["rotations"].grad
         if sh_degree >= 0:
             ref["sh"] = kw["shs"].grad
+        st["margin"] = ex["margin"]
         return g, {k: v.numpy() for k, v in ref.items()}, st
     pytest.skip("no threshold-free scene found")
+
+
+def _frustum_clamped(st):
+    """Gaussians whose view-space x/z or y/z lies outside the 1.3 tan(fov) frustum (float64)."""
+    vm = st["vm"].astype(np.float64).reshape(4, 4)  # row-vector convention: p_view = [p, 1] @ vm
+    pv = np.concatenate([st["means3D"].astype(np.float64), np.ones((st["P"], 1))], 1) @ vm
+    return ((np.abs(pv[:, 0] / pv[:, 2]) > 1.3 * st["tanfovx"]) |
+            (np.abs(pv[:, 1] / pv[:, 2]) > 1.3 * st["tanfovy"]))
 
 
 def _close(name, got, ref, rel=2e-4):
@@ -120,14 +131,24 @@ def _close(name, got, ref, rel=2e-4):
     assert not bad.any(), f"{name}: {bad.sum()} mismatches, worst {np.abs(got - ref)[bad].max():.3g} (scale {scale:.3g})"
 
 
-@pytest.mark.parametrize("case", ["rgb", "rgb_bg", "cov3d", "sh0", "sh1", "sh2", "sh3"])
+# near / mod17: the camera one unit from the cloud's centre, so some visible Gaussians lie outside the 1.3 tan(fov)
+# frustum (their t.x / t.y are clamped in J), mod17 with scale_modifier 1.7 on top: the two gradient rules
+# dense_torch.py emulates (a clamped t.x is a constant; dL/dscale without the modifier)
+NEAR = dict(P=60, yaw=25.0, height=0.1, distance=1.0)
+
+
+@pytest.mark.parametrize("case", ["rgb", "rgb_bg", "cov3d", "sh0", "sh1", "sh2", "sh3", "near", "mod17"])
 def test_backward_matches_autograd(case):
     kw = dict(rgb={}, rgb_bg=dict(bg=(0.3, 0.6, 0.9)), cov3d=dict(use_cov3D=True),
               sh0=dict(sh_degree=0), sh1=dict(sh_degree=1), sh2=dict(sh_degree=2),
-              sh3=dict(sh_degree=3))[case]
+              sh3=dict(sh_degree=3), near=NEAR, mod17=dict(NEAR, scale_modifier=1.7))[case]
     g, ref, st = _autograd_case(seed=7, **kw)
     vis = st["radii"] > 0
     assert vis.sum() > 10
+    assert st["margin"] >= 1e-3
+    if case in ("near", "mod17"):
+        hit = vis & _frustum_clamped(st) & np.any(g["means3D"] != 0, axis=1)
+        assert hit.sum() >= 1, "no visible frustum-clamped Gaussian with a gradient"
     _close("means2D", g["means2D"][:, :2], ref["means2D"])
     assert not g["means2D"][:, 2].any()
     _close("opacities", g["opacities"], ref["opacities"])
