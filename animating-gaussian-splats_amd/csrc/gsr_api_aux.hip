@@ -1,7 +1,8 @@
 // gsr_api_aux.hip -- C ABI of libgsr (declared in include/gsr.h): the entry points beside the
-// rasterizer -- fused L1 + SSIM, k-nearest neighbours and the rigidity loss, densification, fused
-// Adam and the camera-frame packing.  Argument validation and workspace carving; the kernels are in
-// gsr_loss.hip, gsr_rigidity.hip, gsr_densify.hip, gsr_adam.hip and gsr_io.hip.
+// rasterizer -- fused L1 + SSIM, k-nearest neighbours and the rigidity loss, the deformation network's
+// input layer, densification, fused Adam and the camera-frame packing.  Argument validation and
+// workspace carving; the kernels are in gsr_loss.hip, gsr_rigidity.hip, gsr_deform.hip,
+// gsr_densify.hip, gsr_adam.hip and gsr_io.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -63,6 +64,14 @@ int check_rigid(int P, int F, int k) {
     if (P < 0 || F < 0 || k < 0) return fail(GSR_ERR_ARG, "rigidity: negative size");
     if (F > P) return fail(GSR_ERR_ARG, "rigidity: %d foreground rows of %d Gaussians", F, P);
     if ((size_t)F * (size_t)k >= (size_t)1 << 31) return fail(GSR_ERR_UNSUPPORTED, "rigidity: more than 2^31 edges");
+    return GSR_OK;
+}
+
+constexpr int kDeformMaxH = 512;
+int check_deform(int P, int H) {
+    if (P < 0) return fail(GSR_ERR_ARG, "deform_in: P must be >= 0");
+    if (H < 1 || H > kDeformMaxH)
+        return fail(GSR_ERR_UNSUPPORTED, "deform_in: hidden dimension %d (1 to %d supported)", H, kDeformMaxH);
     return GSR_OK;
 }
 
@@ -176,6 +185,73 @@ int gsr_rigidity_backward(int P, int F, int k, const int *row_to_foreground, con
     HIP_TRY(launch_rigid_bwd(P, F, k, row_to_foreground, reverse_offsets, reverse_edges,
                              (const float *)(base + L.save_u), (const float *)(base + L.save_m),
                              (const float *)(base + L.save_q), dL_dloss, dL_dmeans, dL_drotation_quaternions, s));
+    return GSR_OK;
+}
+
+// ---- deformation network input layer ----------------------------------------------------------
+static_assert(kPosencRangeBlocks == GSR_POSENC_RANGE_BLOCKS, "the header's workspace size follows the kernel's grid");
+
+int gsr_posenc_ranges(int P, const float *means, const float *rotation_quaternions, float *partial,
+                      float *out_ranges, void *stream) {
+    if (P < 1) return fail(GSR_ERR_ARG, "posenc: the ranges of an empty cloud are undefined (P = %d)", P);
+    if (!means || !rotation_quaternions || !partial || !out_ranges) return fail(GSR_ERR_ARG, "posenc: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "posenc_ranges");
+    HIP_TRY(launch_posenc_ranges(P, means, rotation_quaternions, partial, out_ranges, s));
+    return GSR_OK;
+}
+
+int gsr_posenc_forward(int P, const float *means, const float *rotation_quaternions, const float *ranges,
+                       float *out_encoding, void *stream) {
+    if (P < 0) return fail(GSR_ERR_ARG, "posenc: P must be >= 0");
+    if (P == 0) return GSR_OK;
+    if (!means || !rotation_quaternions || !ranges || !out_encoding) return fail(GSR_ERR_ARG, "posenc: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "posenc");
+    HIP_TRY(launch_posenc(P, means, rotation_quaternions, ranges, out_encoding, s));
+    return GSR_OK;
+}
+
+int gsr_deform_in_forward(int P, int H, const float *initial_means, const float *initial_rotation_quaternions,
+                          const float *initial_ranges, const float *previous_means,
+                          const float *previous_rotation_quaternions, const float *previous_ranges, float progress,
+                          const float *weight, const float *bias, float *out, void *stream) {
+    int rc = check_deform(P, H);
+    if (rc) return rc;
+    if (P == 0) return GSR_OK;
+    if (!initial_means || !initial_rotation_quaternions || !initial_ranges || !previous_means ||
+        !previous_rotation_quaternions || !previous_ranges || !weight || !bias || !out)
+        return fail(GSR_ERR_ARG, "deform_in: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "deform_in_fwd");
+    HIP_TRY(launch_deform_in_fwd(P, H, initial_means, initial_rotation_quaternions, initial_ranges, previous_means,
+                                 previous_rotation_quaternions, previous_ranges, progress, weight, bias, out, s));
+    return GSR_OK;
+}
+
+size_t gsr_deform_in_workspace_bytes(int P, int H, int max_blocks) {
+    if (P <= 0 || H <= 0) return 0;
+    return align256(sizeof(float) * deform_in_partial_floats(P, H, max_blocks));
+}
+
+int gsr_deform_in_backward(int P, int H, const float *initial_means, const float *initial_rotation_quaternions,
+                           const float *initial_ranges, const float *previous_means,
+                           const float *previous_rotation_quaternions, const float *previous_ranges, float progress,
+                           const float *dL_dout, void *workspace, int max_blocks, float *dL_dweight,
+                           float *dL_dbias, void *stream) {
+    int rc = check_deform(P, H);
+    if (rc) return rc;
+    if (max_blocks < 0) return fail(GSR_ERR_ARG, "deform_in: max_blocks must be >= 0 (0: automatic)");
+    if (!dL_dweight && !dL_dbias) return GSR_OK;
+    if (P == 0) return fail(GSR_ERR_ARG, "deform_in: no rows to sum the gradient over");
+    if (!initial_means || !initial_rotation_quaternions || !initial_ranges || !previous_means ||
+        !previous_rotation_quaternions || !previous_ranges || !dL_dout || !workspace)
+        return fail(GSR_ERR_ARG, "deform_in: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "deform_in_bwd");
+    HIP_TRY(launch_deform_in_bwd(P, H, initial_means, initial_rotation_quaternions, initial_ranges, previous_means,
+                                 previous_rotation_quaternions, previous_ranges, progress, dL_dout, (float *)workspace,
+                                 max_blocks, dL_dweight, dL_dbias, s));
     return GSR_OK;
 }
 

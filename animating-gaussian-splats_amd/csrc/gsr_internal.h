@@ -137,6 +137,21 @@ hipError_t launch_rigid_bwd(int P, int F, int k, const int *row_to_fg, const int
                             const float *save_u, const float *save_m, const float *save_q, const float *g_loss,
                             float *dmeans, float *dquats, hipStream_t s);
 
+// deformation network input layer (gsr_deform.hip): i* initial, p* previous (means, quats, ranges)
+constexpr int kDeformAutoBlocks = 256;  // persistent backward workgroups when the caller sets no bound (one per CU)
+constexpr int kPosencRangeBlocks = 256;  // = GSR_POSENC_RANGE_BLOCKS: workgroups (partials) of the range reduction
+hipError_t launch_posenc_ranges(int P, const float *means, const float *quats, float *partial, float *ranges,
+                                hipStream_t s);
+hipError_t launch_posenc(int P, const float *means, const float *quats, const float *ranges, float *out, hipStream_t s);
+hipError_t launch_deform_in_fwd(int P, int H, const float *im, const float *iq, const float *ir, const float *pm,
+                                const float *pq, const float *pr, float progress, const float *W, const float *bias,
+                                float *Y, hipStream_t s);
+int deform_in_blocks(int P, int max_blocks);
+size_t deform_in_partial_floats(int P, int H, int max_blocks);
+hipError_t launch_deform_in_bwd(int P, int H, const float *im, const float *iq, const float *ir, const float *pm,
+                                const float *pq, const float *pr, float progress, const float *dY, float *partial,
+                                int max_blocks, float *dW, float *db, hipStream_t s);
+
 // densification (gsr_densify.hip)
 struct DensArgs {
     int P, prune_big;

@@ -401,6 +401,43 @@ int gsr_rigidity_backward(int P, int F, int k, const int *row_to_foreground, con
                           const int *reverse_edges, const void *scratch, const float *dL_dloss, float *dL_dmeans,
                           float *dL_drotation_quaternions, void *stream);
 
+/* ---- Deformation network input layer (additive to ABI 21) --------------------------------------
+ * The encoded input of train.py's DeformationNetwork and its first linear layer.  An encoding takes
+ * means (P, 3), rotation_quaternions (P, 4, raw) and ranges, 14 DEVICE floats: lo[7] the column minima
+ * (means xyz, then quaternion wxyz), hi[7] the column maxima of (x - lo).  Per column xn = (2 (x - lo)) /
+ * hi - 1 in fp32 (a constant column gives NaN, as in the reference); PositionalEncoding (train.py:113-127)
+ * with f_l = 2^l pi, 10 frequencies for the means and 4 for the quaternions: feature (2 l) C + c =
+ * sin(f_l xn_c), feature (2 l + 1) C + c = the cosine OF THAT SINE.
+ * gsr_posenc_forward writes the (P, 92) encoding [means 60 | quaternions 32]
+ * (normalize_and_encode_means_and_rotations, train.py:185-204).
+ * gsr_posenc_ranges computes the 14 range floats of a cloud (P >= 1) on the device: the exact column
+ * minima, and hi = (column maximum) - lo, which equals max (x - lo) because the fp32 subtraction is
+ * monotone.  partial: GSR_POSENC_RANGE_BLOCKS x 14 floats of device workspace. */
+#define GSR_POSENC_RANGE_BLOCKS 256
+int gsr_posenc_ranges(int P, const float *means, const float *rotation_quaternions, float *partial,
+                      float *out_ranges, void *stream);
+int gsr_posenc_forward(int P, const float *means, const float *rotation_quaternions, const float *ranges,
+                       float *out_encoding, void *stream);
+/* out (P, H) = X (P, 192) weight^T + bias with X = [enc(initial) 92 | enc(previous) 92 | enc(progress) 8]
+ * (train.py:96-104) never written to memory; weight (H, 192) row-major and bias (H) as in nn.Linear,
+ * progress = timestep / timestep_count encoded unnormalised with 4 frequencies.  1 <= H <= 512.  The
+ * summation order is fixed: two runs are bitwise equal. */
+int gsr_deform_in_forward(int P, int H, const float *initial_means, const float *initial_rotation_quaternions,
+                          const float *initial_ranges, const float *previous_means,
+                          const float *previous_rotation_quaternions, const float *previous_ranges, float progress,
+                          const float *weight, const float *bias, float *out, void *stream);
+/* dL_dweight (H, 192) = dL_dout^T X and dL_dbias (H) = column sums of dL_dout (either may be NULL), X
+ * recomputed; the encoded inputs get no gradient (the reference detaches them).  A fixed grid of
+ * workgroups (max_blocks > 0: at most that many; 0: automatic) each writes one partial to workspace
+ * (gsr_deform_in_workspace_bytes with the same P, H, max_blocks), summed in workgroup order: no float
+ * atomics, two runs are bitwise equal. */
+size_t gsr_deform_in_workspace_bytes(int P, int H, int max_blocks);
+int gsr_deform_in_backward(int P, int H, const float *initial_means, const float *initial_rotation_quaternions,
+                           const float *initial_ranges, const float *previous_means,
+                           const float *previous_rotation_quaternions, const float *previous_ranges, float progress,
+                           const float *dL_dout, void *workspace, int max_blocks, float *dL_dweight,
+                           float *dL_dbias, void *stream);
+
 /* ---- Densification: statistics, clone / split / prune with Adam state surgery (ABI >= 4) ------
  * SURVEY.md 8(f) row 2.  Replaces update_max_2d_radii_and_visibility_mask (densify.py:154-162),
  * accumulate_mean_2d_gradients (external.py:113-124) and the body of densify_gaussians
@@ -492,7 +529,8 @@ int gsr_views_pack(int frames, int H, int W, const uint8_t *rgb, const uint8_t *
 
 /* Per-phase device timing with HIP events recorded on the call's stream (off by default).
  * Phases: "preprocess", "bin_count", "bin_scan", "bin_emit", "tile_sort", "render_fwd",
- * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "knn", "rigidity_fwd", "rigidity_bwd".  gsr_profile_read synchronises on the recorded events. */
+ * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "knn", "rigidity_fwd", "rigidity_bwd",
+ * "posenc_ranges", "posenc", "deform_in_fwd", "deform_in_bwd".  gsr_profile_read synchronises on the recorded events. */
 int gsr_profile_enable(int on);
 /* Restrict event recording to a comma-separated list of phases (NULL or "" = every phase), so a
  * timed region can carry the events of one kernel only.  Host-side timers are unaffected. */

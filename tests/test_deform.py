@@ -1,0 +1,320 @@
+"""The deformation network's input side (splat_deform, csrc/gsr_deform.hip).
+
+CPU: the restatements of tests/deform_ref.py reproduce what the reference itself computed
+(tests/golden/reference_deform.npz, written by tests/golden/gen_golden_deform.py); the module has the
+reference's state_dict and refuses CPU tensors and bad shapes.  GPU: the HIP kernels against the float64
+restatement.  "Project band": |got - ref| <= 1e-4 |ref| + 1e-6 max|ref| with no value outside (the band of
+tests/test_rigidity.py); "golden band": 2e-4 |ref| + 2e-5 max|ref| for values the reference saved in fp32.
+"""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import deform_ref as DR
+import splat_deform as D
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLD = np.load(os.path.join(HERE, "golden", "reference_deform.npz"))
+PROGRESS = 3 / 7
+ULP2 = 2.4e-7  # 2 ulp of 1.0: every feature lies in [-1, 1]
+
+
+def _t(name):
+    return torch.from_numpy(GOLD[name])
+
+
+def _gold_clouds(device="cpu"):
+    return ({"means": _t("initial_means").to(device), "rotation_quaternions": _t("initial_rotation_quaternions").to(device)},
+            {"means": _t("previous_means").to(device), "rotation_quaternions": _t("previous_rotation_quaternions").to(device)})
+
+
+def _gold_progress():
+    timestep, count = GOLD["timestep"]
+    return int(timestep) / int(count)
+
+
+def _gold_state():
+    return {str(n): _t(f"state/{n}") for n in GOLD["state_names"]}
+
+
+def _band(name, got, ref, rtol=1e-4, atol_frac=1e-6, floor=0.0):
+    got = np.asarray(got.detach().cpu() if torch.is_tensor(got) else got, np.float64)
+    ref = np.asarray(ref.detach().cpu() if torch.is_tensor(ref) else ref, np.float64)
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    assert np.isfinite(ref).all() and np.isfinite(got).all(), name
+    scale = np.abs(ref).max()
+    err = np.abs(got - ref)
+    bad = err > np.maximum(rtol * np.abs(ref) + atol_frac * scale, floor)
+    print(f"{name}: worst {err.max():.3e} = {err.max() / max(scale, 1e-300):.3e} max|ref| ({scale:.3e}), "
+          f"floor {floor:.3e}, outside {bad.sum()}/{bad.size}")
+    assert not bad.any(), f"{name}: {bad.sum()}/{bad.size} outside the band, worst {err.max():.3g} (scale {scale:.3g})"
+
+
+@functools.lru_cache(maxsize=None)
+def _clouds(P, constant_column=False):
+    """Seeded (initial, previous) clouds on the CPU; ``constant_column``: the initial y and the previous
+    quaternion x are the same in every row (their normalisation is 0 / 0)."""
+    g = torch.Generator().manual_seed(1000 + P)
+    initial = {"means": (torch.rand(P, 3, generator=g) - 0.5) * 3.0, "rotation_quaternions": torch.randn(P, 4, generator=g)}
+    previous = {"means": initial["means"] + 0.05 * torch.randn(P, 3, generator=g),
+                "rotation_quaternions": initial["rotation_quaternions"] + 0.1 * torch.randn(P, 4, generator=g)}
+    if constant_column:
+        initial["means"][:, 1] = 0.25
+        previous["rotation_quaternions"][:, 1] = -0.5
+    return initial, previous
+
+
+def _to(cloud, device):
+    return {k: v.to(device) for k, v in cloud.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _layer(P, H):
+    """Seeded fc_in weights, bias and upstream gradient for a (P, H) case, on the CPU."""
+    g = torch.Generator().manual_seed(7 * P + H)
+    bound = 1 / 192 ** 0.5  # nn.Linear's initialisation range
+    return ((torch.rand(H, 192, generator=g) * 2 - 1) * bound, (torch.rand(H, generator=g) * 2 - 1) * bound,
+            torch.randn(P, H, generator=g))
+
+
+# ---- CPU ------------------------------------------------------------------------------------------
+def test_encoding_restatement_reproduces_reference():
+    initial, previous = _gold_clouds()
+    for cloud, key in ((initial, "encoded_initial"), (previous, "encoded_previous")):
+        e32 = DR.encode_means_and_rotations(cloud["means"], cloud["rotation_quaternions"], torch.float32)
+        assert e32.dtype == torch.float32 and np.array_equal(e32.numpy(), GOLD[key]), key
+        e64 = DR.encode_means_and_rotations(cloud["means"], cloud["rotation_quaternions"], torch.float64)
+        err = np.abs(e64.numpy() - GOLD[key].astype(np.float64)).max()
+        print(f"{key}: float64 restatement vs reference {err:.3e}")
+        assert e64.dtype == torch.float64 and err <= ULP2
+    p32 = DR.encode_progress(_gold_progress(), 5, "cpu", torch.float32)
+    assert np.array_equal(p32.numpy(), np.broadcast_to(GOLD["encoded_progress"], (5, 8)))
+    p64 = DR.encode_progress(_gold_progress(), 1, "cpu", torch.float64)
+    assert np.abs(p64.numpy()[0] - GOLD["encoded_progress"]).max() <= ULP2
+
+
+def test_network_restatement_reproduces_reference():
+    initial, previous = _gold_clouds()
+    H = GOLD["state/fc_in.weight"].shape[0]
+    net = DR.TorchDeformationNetwork(H, 1)
+    net.load_state_dict(_gold_state())
+    net.train()
+    out, fc_in_out, grads = DR.network_output_and_grads(net, initial, previous, _gold_progress(), _t("upstream"),
+                                                        torch.float32)
+    _band("fc_in_output", fc_in_out, GOLD["fc_in_output"], 2e-4, 2e-5)
+    _band("output", out, GOLD["output"], 2e-4, 2e-5)
+    for name, g in grads.items():
+        _band(f"grad {name}", g, GOLD[f"grad/{name}"], 2e-4, 2e-5)
+
+
+def test_stale_library_is_a_rebuild_error(monkeypatch):
+    """A libgsr.so without the entry points raises on first use of the feature, naming the remedy."""
+    from diff_gaussian_rasterization import _C
+    _C.load_library()
+    assert _C._DEFORM_MISSING is None and _C.deform_library() is _C.load_library()
+    monkeypatch.setattr(_C, "_DEFORM_MISSING", "undefined symbol: gsr_deform_in_forward")
+    with pytest.raises(RuntimeError, match="rebuild"):
+        _C.deform_library()
+
+
+def test_module_contract():
+    net = D.DeformationNetwork(32, 1)
+    state = net.state_dict()
+    assert list(state.keys()) == [str(n) for n in GOLD["state_names"]]
+    for name, shape in zip(GOLD["state_names"], GOLD["state_shapes"]):
+        want = tuple(int(d) for d in str(shape).split(",") if d)
+        assert tuple(state[str(name)].shape) == want, name
+    net.load_state_dict(_gold_state())  # a reference checkpoint loads
+    initial, previous = _gold_clouds()
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        D.encode_means_and_rotations(initial)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        D.deform_input_layer(net.fc_in.weight, net.fc_in.bias, initial, previous, PROGRESS)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        net(initial, previous, 3, 7)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        D.update_gaussian_cloud_parameters(net, initial, previous, 3, 7)
+    with pytest.raises(ValueError):
+        D.DeformationNetwork(513, 1)
+    with pytest.raises(ValueError):
+        D.deform_input_layer(torch.zeros(0, 192), torch.zeros(0), initial, previous, PROGRESS)
+    with pytest.raises(ValueError):
+        D.deform_input_layer(torch.zeros(513, 192), torch.zeros(513), initial, previous, PROGRESS)
+    with pytest.raises(ValueError):
+        D.deform_input_layer(torch.zeros(32, 191), torch.zeros(32), initial, previous, PROGRESS)
+    with pytest.raises(ValueError):
+        D.deform_input_layer(torch.zeros(32, 192), torch.zeros(31), initial, previous, PROGRESS)
+    with pytest.raises(ValueError):
+        D.deform_input_layer(torch.zeros(32, 192, dtype=torch.float64), torch.zeros(32), initial, previous, PROGRESS)
+    with pytest.raises(ValueError):
+        D.deform_input_layer(torch.zeros(32, 192), torch.zeros(32), initial, {"means": previous["means"][:5],
+                             "rotation_quaternions": previous["rotation_quaternions"][:5]}, PROGRESS)
+    with pytest.raises(ValueError):
+        D.encode_means_and_rotations({"means": torch.zeros(4, 4), "rotation_quaternions": torch.zeros(4, 4)})
+    with pytest.raises(ValueError):
+        D.encode_means_and_rotations({"means": torch.zeros(4, 3, dtype=torch.float64),
+                                      "rotation_quaternions": torch.zeros(4, 4)})
+
+
+# ---- GPU: the encoding ----------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("P,constant", [(1, False), (63, False), (63, True), (257, False), (4099, False)])
+def test_encode_means_and_rotations(cuda, P, constant):
+    """Against the float64 restatement; the yardstick is the float32 torch restatement's own worst error
+    on this device on the same inputs, the kernel may have max(2 x that, 2.4e-7)."""
+    cloud = _to(_clouds(P, constant)[0], cuda)
+    got = D.encode_means_and_rotations(cloud)
+    assert got.shape == (P, 92) and got.dtype == torch.float32
+    r32 = DR.encode_means_and_rotations(cloud["means"], cloud["rotation_quaternions"], torch.float32)
+    r64 = DR.encode_means_and_rotations(cloud["means"], cloud["rotation_quaternions"], torch.float64)
+    nan = torch.isnan(r64)
+    assert torch.equal(torch.isnan(got), nan) and torch.equal(torch.isnan(r32), nan)
+    if P == 1:
+        assert bool(nan.all())  # every column is constant: 0 / 0
+        return
+    assert bool(nan.any()) == constant
+    if constant:  # exactly the sine and cosine slots of the constant column (mean y: column 1 of 3)
+        cols = torch.zeros(92, dtype=torch.bool)
+        cols[[j * 3 + 1 for j in range(20)]] = True
+        assert torch.equal(nan.cpu(), cols.expand(P, 92))
+    ok = ~nan
+    yard = float((r32.double() - r64)[ok].abs().max())
+    err = float((got.double() - r64)[ok].abs().max())
+    print(f"P={P} constant={constant}: kernel {err:.3e}, float32 torch restatement {yard:.3e}")
+    assert err <= max(2 * yard, ULP2)
+
+
+# ---- GPU: the fused input layer -------------------------------------------------------------------
+def _layer_case(cuda, P, H):
+    initial, previous = (_to(c, cuda) for c in _clouds(P))
+    w, b, up = (t.to(cuda) for t in _layer(P, H))
+    x64 = DR.input_matrix(initial, previous, PROGRESS, torch.float64)
+    return initial, previous, w, b, up, x64
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P,H", [(63, 64), (257, 128), (1031, 40), (4099, 64)])
+def test_fused_forward(cuda, P, H):
+    initial, previous, w, b, _, x64 = _layer_case(cuda, P, H)
+    got = D.deform_input_layer(w, b, initial, previous, PROGRESS)
+    assert got.shape == (P, H) and got.dtype == torch.float32
+    _band(f"fc_in output ({P}, {H})", got, x64 @ w.double().t() + b.double())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_blocks", [0, 2])
+@pytest.mark.parametrize("P,H", [(63, 64), (257, 128), (1031, 40)])
+def test_fused_backward(cuda, P, H, max_blocks):
+    initial, previous, w, b, up, x64 = _layer_case(cuda, P, H)
+    initial = {k: v.clone().requires_grad_(True) for k, v in initial.items()}
+    previous = {k: v.clone().requires_grad_(True) for k, v in previous.items()}
+    w, b = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    out = D.deform_input_layer(w, b, initial, previous, PROGRESS, max_blocks=max_blocks)
+    out.backward(up)
+    _band(f"dW ({P}, {H}, max_blocks={max_blocks})", w.grad, up.double().t() @ x64)
+    _band(f"db ({P}, {H}, max_blocks={max_blocks})", b.grad, up.double().sum(0))
+    pe64 = DR.encode_progress(PROGRESS, 1, cuda, torch.float64)[0]
+    _band("dW[:, 184:] = enc(progress) db", w.grad[:, 184:], b.grad.double()[:, None] * pe64[None, :])
+    for cloud in (initial, previous):
+        assert all(v.grad is None for v in cloud.values())  # the encoded parameters are detached
+
+
+@pytest.mark.gpu
+def test_golden_fc_in(cuda):
+    initial, previous = _gold_clouds(cuda)
+    w = _t("state/fc_in.weight").to(cuda).requires_grad_(True)
+    b = _t("state/fc_in.bias").to(cuda).requires_grad_(True)
+    out = D.deform_input_layer(w, b, initial, previous, _gold_progress())
+    _band("golden fc_in output", out, GOLD["fc_in_output"], 2e-4, 2e-5)
+    out.backward(_t("grad_fc_in_output").to(cuda))  # the gradient that reached fc_in's output in the reference
+    _band("golden grad fc_in.weight", w.grad, GOLD["grad/fc_in.weight"], 2e-4, 2e-5)
+    _band("golden grad fc_in.bias", b.grad, GOLD["grad/fc_in.bias"], 2e-4, 2e-5)
+
+
+# ---- GPU: the whole network -----------------------------------------------------------------------
+@pytest.mark.gpu
+def test_whole_network(cuda):
+    """P = 1031, H = 64, 2 blocks, train mode, against the float64 torch-only network with the same
+    state_dict.  Per tensor the yardstick is the float32 torch-only network's worst error against float64
+    on this device; the fused network may have twice that or the project band, whichever is larger."""
+    P, H, blocks = 1031, 64, 2
+    initial, previous = (_to(c, cuda) for c in _clouds(P))
+    torch.manual_seed(5)
+    fused = D.DeformationNetwork(H, blocks).to(cuda).train()
+    state = {k: v.clone() for k, v in fused.state_dict().items()}
+    up = torch.randn(P, 7, generator=torch.Generator().manual_seed(6)).to(cuda)
+    base = torch.cat((initial["means"], initial["rotation_quaternions"]), dim=1)
+
+    def torch_only(dtype):
+        net = DR.TorchDeformationNetwork(H, blocks).to(cuda).to(dtype).train()
+        net.load_state_dict(state)  # names and shapes match; values are cast
+        out = net(DR.input_matrix(initial, previous, PROGRESS, dtype), base.to(dtype))
+        y = base.to(dtype) + 0.01 * out  # train.py:295-307
+        (y * up.to(dtype)).sum().backward()
+        return net, y.detach(), {n: p.grad for n, p in net.named_parameters()}
+
+    net64, y64, g64 = torch_only(torch.float64)
+    _, y32, g32 = torch_only(torch.float32)
+
+    extra = {"colors": torch.rand(P, 3, device=cuda), "segmentation_masks": torch.rand(P, 3, device=cuda)}
+    deltas = []
+    hook = fused.register_forward_hook(lambda m, i, o: deltas.append(o.detach()))
+    updated = D.update_gaussian_cloud_parameters(fused, {**initial, **extra}, previous, 3, 7)
+    hook.remove()
+    assert set(updated) == {"means", "rotation_quaternions", "colors", "segmentation_masks"}
+    assert updated["colors"] is extra["colors"] and updated["segmentation_masks"] is extra["segmentation_masks"]
+    y = torch.cat((updated["means"], updated["rotation_quaternions"]), dim=1)
+    (y * up).sum().backward()
+    assert len(deltas) == 1 and torch.equal(y.detach(), base + deltas[0] * 0.01)
+
+    def check(name, got, r32, r64):
+        yard = float((r32.double() - r64).abs().max())
+        _band(name, got, r64, floor=2 * yard)
+
+    check("updated means and quaternions", y, y32, y64)
+    for name, p in fused.named_parameters():
+        check(f"grad {name}", p.grad, g32[name], g64[name])
+
+    # the state_dict round-trips into the torch-only network and back
+    net32 = DR.TorchDeformationNetwork(H, blocks)
+    net32.load_state_dict(fused.state_dict())
+    back = D.DeformationNetwork(H, blocks)
+    back.load_state_dict(net32.state_dict())
+    for k, v in fused.state_dict().items():
+        assert torch.equal(back.state_dict()[k], v.cpu()), k
+    assert net64.fc_in.weight.dtype == torch.float64
+
+
+# ---- GPU: repeatability, no_grad ------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("P,H", [(4099, 64), (1031, 40)])
+def test_bitwise_repeatable(cuda, P, H):
+    initial, previous, w, b, up, _ = _layer_case(cuda, P, H)
+
+    def run():
+        wp, bp = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        out = D.deform_input_layer(wp, bp, initial, previous, PROGRESS, max_blocks=2)
+        out.backward(up)
+        return out.detach(), wp.grad, bp.grad
+
+    for a, c in zip(run(), run()):
+        assert torch.equal(a, c)
+
+
+@pytest.mark.gpu
+def test_no_grad_saves_nothing(cuda):
+    P, H = 257, 128
+    initial, previous, w, b, _, _ = _layer_case(cuda, P, H)
+    w, b = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    saved = []
+    with torch.autograd.graph.saved_tensors_hooks(lambda t: saved.append(t) or t, lambda t: t):
+        with torch.no_grad():
+            quiet = D.deform_input_layer(w, b, initial, previous, PROGRESS)
+        assert saved == [] and quiet.grad_fn is None and not quiet.requires_grad
+        loud = D.deform_input_layer(w, b, initial, previous, PROGRESS)
+        assert len(saved) == 6 and loud.grad_fn is not None
+    assert sum(t.numel() for t in saved) == 2 * (7 * P + 14)  # the 14-float inputs and the ranges, nothing else
+    assert torch.equal(quiet, loud.detach())
