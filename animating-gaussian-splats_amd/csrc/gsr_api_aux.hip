@@ -1,8 +1,8 @@
 // gsr_api_aux.hip -- C ABI of libgsr (declared in include/gsr.h): the entry points beside the
 // rasterizer -- fused L1 + SSIM, k-nearest neighbours and the rigidity loss, the deformation network's
-// input layer, densification, fused Adam and the camera-frame packing.  Argument validation and
-// workspace carving; the kernels are in gsr_loss.hip, gsr_rigidity.hip, gsr_deform.hip,
-// gsr_densify.hip, gsr_adam.hip and gsr_io.hip.
+// input layer and residual blocks, densification, fused Adam and the camera-frame packing.  Argument
+// validation and workspace carving; the kernels are in gsr_loss.hip, gsr_rigidity.hip, gsr_deform.hip,
+// gsr_resblock.hip, gsr_densify.hip, gsr_adam.hip and gsr_io.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -72,6 +72,14 @@ int check_deform(int P, int H) {
     if (P < 0) return fail(GSR_ERR_ARG, "deform_in: P must be >= 0");
     if (H < 1 || H > kDeformMaxH)
         return fail(GSR_ERR_UNSUPPORTED, "deform_in: hidden dimension %d (1 to %d supported)", H, kDeformMaxH);
+    return GSR_OK;
+}
+
+int check_resblock(int P, int H, int max_blocks) {
+    if (P < 2) return fail(GSR_ERR_ARG, "resblock: batch statistics need P >= 2 rows (got %d)", P);
+    if (H < 1 || H > kResblockMaxH)
+        return fail(GSR_ERR_ARG, "resblock: hidden dimension %d (1 to %d supported)", H, kResblockMaxH);
+    if (max_blocks < 0) return fail(GSR_ERR_ARG, "resblock: max_blocks must be >= 0 (0: automatic)");
     return GSR_OK;
 }
 
@@ -252,6 +260,53 @@ int gsr_deform_in_backward(int P, int H, const float *initial_means, const float
     HIP_TRY(launch_deform_in_bwd(P, H, initial_means, initial_rotation_quaternions, initial_ranges, previous_means,
                                  previous_rotation_quaternions, previous_ranges, progress, dL_dout, (float *)workspace,
                                  max_blocks, dL_dweight, dL_dbias, s));
+    return GSR_OK;
+}
+
+// ---- deformation network residual blocks ------------------------------------------------------
+size_t gsr_resblock_workspace_bytes(int P, int H, int max_blocks, int backward) {
+    if (P < 2 || H < 1 || H > kResblockMaxH || max_blocks < 0) return 0;
+    return ResblockWorkspace(P, H, max_blocks, backward != 0).total;
+}
+
+int gsr_resblock_forward(int P, int H, const float *x, const float *fc1_weight, const float *bn1_weight,
+                         const float *bn1_bias, const float *fc2_weight, const float *bn2_weight,
+                         const float *bn2_bias, float eps1, float eps2, float momentum1, float momentum2,
+                         float *bn1_running_mean, float *bn1_running_var, float *bn2_running_mean,
+                         float *bn2_running_var, void *workspace, int max_blocks, float *y1, float *y2, float *out,
+                         float *stats, void *stream) {
+    int rc = check_resblock(P, H, max_blocks);
+    if (rc) return rc;
+    if (!x || !fc1_weight || !bn1_weight || !bn1_bias || !fc2_weight || !bn2_weight || !bn2_bias || !workspace ||
+        !y1 || !y2 || !out || !stats)
+        return fail(GSR_ERR_ARG, "resblock: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "resblock_fwd");
+    HIP_TRY(launch_resblock_fwd(P, H, x, fc1_weight, bn1_weight, bn1_bias, fc2_weight, bn2_weight, bn2_bias, eps1, eps2,
+                                momentum1, momentum2, bn1_running_mean, bn1_running_var, bn2_running_mean,
+                                bn2_running_var, (char *)workspace, max_blocks, y1, y2, out, stats, s));
+    return GSR_OK;
+}
+
+int gsr_resblock_backward(int P, int H, const float *x, const float *y1, const float *y2, const float *stats,
+                          const float *fc1_weight, const float *bn1_weight, const float *bn1_bias,
+                          const float *fc2_weight, const float *bn2_weight, const float *bn2_bias,
+                          const float *dL_dout, void *workspace, int max_blocks, float *dL_dx, float *dL_dfc1_weight,
+                          float *dL_dbn1_weight, float *dL_dbn1_bias, float *dL_dfc2_weight, float *dL_dbn2_weight,
+                          float *dL_dbn2_bias, void *stream) {
+    int rc = check_resblock(P, H, max_blocks);
+    if (rc) return rc;
+    if (!dL_dx && !dL_dfc1_weight && !dL_dbn1_weight && !dL_dbn1_bias && !dL_dfc2_weight && !dL_dbn2_weight &&
+        !dL_dbn2_bias)
+        return GSR_OK;
+    if (!x || !y1 || !y2 || !stats || !fc1_weight || !bn1_weight || !bn1_bias || !fc2_weight || !bn2_weight ||
+        !bn2_bias || !dL_dout || !workspace)
+        return fail(GSR_ERR_ARG, "resblock: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "resblock_bwd");
+    HIP_TRY(launch_resblock_bwd(P, H, x, y1, y2, stats, fc1_weight, bn1_weight, bn1_bias, fc2_weight, bn2_weight,
+                                bn2_bias, dL_dout, (char *)workspace, max_blocks, dL_dx, dL_dfc1_weight, dL_dbn1_weight,
+                                dL_dbn1_bias, dL_dfc2_weight, dL_dbn2_weight, dL_dbn2_bias, s));
     return GSR_OK;
 }
 

@@ -152,6 +152,24 @@ hipError_t launch_deform_in_bwd(int P, int H, const float *im, const float *iq, 
                                 const float *pq, const float *pr, float progress, const float *dY, float *partial,
                                 int max_blocks, float *dW, float *db, hipStream_t s);
 
+// deformation network residual blocks (gsr_resblock.hip): stats = mean1, invstd1, mean2, invstd2 (4 H)
+constexpr int kResblockAutoBlocks = 256;  // persistent workgroups when the caller sets no bound (one per CU; twice that for H <= 64)
+constexpr int kResblockMaxH = 128;
+struct ResblockWorkspace {  // byte offsets; the backward's also holds the two transient (P, H) gradients
+    size_t partial_s, partial_w, sums, g_s, g_z1, total;
+    ResblockWorkspace(int P, int H, int max_blocks, bool backward);
+};
+hipError_t launch_resblock_fwd(int P, int H, const float *x, const float *W1, const float *gamma1, const float *beta1,
+                               const float *W2, const float *gamma2, const float *beta2, float eps1, float eps2,
+                               float momentum1, float momentum2, float *running_mean1, float *running_var1,
+                               float *running_mean2, float *running_var2, char *ws, int max_blocks, float *y1, float *y2,
+                               float *out, float *stats, hipStream_t s);
+hipError_t launch_resblock_bwd(int P, int H, const float *x, const float *y1, const float *y2, const float *stats,
+                               const float *W1, const float *gamma1, const float *beta1, const float *W2,
+                               const float *gamma2, const float *beta2, const float *g_out, char *ws, int max_blocks,
+                               float *dx, float *dW1, float *dgamma1, float *dbeta1, float *dW2, float *dgamma2,
+                               float *dbeta2, hipStream_t s);
+
 // densification (gsr_densify.hip)
 struct DensArgs {
     int P, prune_big;

@@ -1,0 +1,593 @@
+// gsr_resblock.hip -- the residual blocks of train.py's deformation network (train.py:57-77), fused:
+//     y1 = x W1^T;  a1 = gelu(bn1(y1));  y2 = a1 W2^T;  out = gelu(bn2(y2) + x)
+// with both BatchNorms on the batch statistics (the reference never calls .eval()), GELU in the exact erf
+// form.  All fp32 on v_mfma_f32_32x32x2_f32 (bit for bit a k-ordered fmaf chain); no float atomics: every
+// reduction over rows is one partial per workgroup, combined in workgroup order, so two runs are bitwise equal.
+//
+// A workgroup of 8 waves takes 64-row tiles (tile = block, block + grid, ...).  H is padded to HP = 32 NT
+// columns (NT = 1 .. 4) with zeros; LDS row strides are HP + 1 (odd: the 32 rows a lane group reads for the
+// MFMA A operand hit 32 banks; B operands and the staging stores are consecutive floats).  The GEMM kernels
+// load the next tile's rows into registers before they multiply the current one, so the loads' latency is
+// behind the MFMAs even with one workgroup per CU (H > 64).
+//
+//   k_res_gemm<NT, PRO>      Y = A W^T with A = X (PRO = false) or gelu(bn(X)) applied on the way into LDS
+//                            (PRO = true).  W staged once, k-major.  Wave w owns rows 32 (w & 1) .. + 31 and
+//                            column tile w >> 1.  Per tile each wave reduces its 32 x 32 result to a per-column
+//                            (mean, M2) about its own mean in registers; the workgroup merges them over its
+//                            tiles with Chan's formula in double and writes one (count, mean, M2) per column.
+//   k_res_stats              merges the workgroups' partials (Chan, double, workgroup order: lanes take
+//                            consecutive chunks, then neighbours merge) into mean and 1 / sqrt(var + eps), and
+//                            blends the running statistics (unbiased variance) as torch does.
+//   k_res_out                out = gelu(bn2(y2) + x), float4 where H % 4 == 0.
+//   k_res_bwd_out            g_s = g_out gelu'(bn2(y2) + x) and per-workgroup column sums of g_s and g_s xhat2.
+//   k_res_colsum             those partials (double) summed in workgroup order: dbeta, dgamma.
+//   k_res_bwd_gemm<NT, ST>   G = BN-backward of (g_in, y) formed into LDS; dW += G^T A accumulated in registers
+//                            over the workgroup's tiles (A = gelu(bn1(y1)) recomputed for stage 2, x for stage
+//                            1), one H x H partial per workgroup; R = G W, then stage 2 writes g_z1 = R gelu'(bn1(y1))
+//                            and the column sums of g_z1 and g_z1 xhat1, stage 1 writes g_x = R + g_s.
+//   k_res_reduce_w           sums the dW partials in workgroup order.
+#include "gsr_common.h"
+#include "gsr_internal.h"
+
+namespace gsr {
+
+namespace {
+constexpr int kRows = 64, kThreads = 512, kEwThreads = 256;
+constexpr int kOutBlocks = 1024;  // workgroups of k_res_bwd_out when the caller sets no bound
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct BnCols { const float *mean, *invstd, *gamma, *beta; };
+
+__device__ inline float gelu_f(float t) { return (t * 0.5f) * (1.0f + erff(t * 0.70710678118654752440f)); }
+// Phi(t) + t phi(t)
+__device__ inline float gelu_grad(float t) {
+    const float cdf = 0.5f * (1.0f + erff(t * 0.70710678118654752440f));
+    const float pdf = 0.39894228040143267794f * expf(-0.5f * (t * t));
+    return cdf + t * pdf;
+}
+
+// (n, mean, M2) of a set followed by (nb, mb, m2b) of the next
+__device__ inline void chan(double &n, double &mean, double &m2, double nb, double mb, double m2b) {
+    if (nb == 0.0) return;
+    if (n == 0.0) { n = nb; mean = mb; m2 = m2b; return; }
+    const double tot = n + nb, d = mb - mean;
+    mean = mean + d * (nb / tot);
+    m2 = m2 + m2b + d * d * (n * nb / tot);
+    n = tot;
+}
+
+// row of accumulator register r of a 32 x 32 MFMA result (the column is lane & 31)
+__device__ inline int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+}  // namespace
+
+template <int NT, bool PRO>
+__global__ __launch_bounds__(kThreads) void k_res_gemm(int P, int H, int tiles, const float *__restrict__ X,
+                                                       const float *__restrict__ W, BnCols bn, float *__restrict__ Y,
+                                                       double *__restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) float s_lds[];
+    constexpr int HP = NT * 32, XS = HP + 1, WS = HP + 1;
+    float *Xs = s_lds;               // kRows * XS
+    float *Ws = Xs + kRows * XS;     // HP * WS, k-major: Ws[k][j] = W[j][k]
+    float *cols = Ws + HP * WS;      // 4 * HP: mean, invstd, gamma, beta of the prologue's BatchNorm
+    float *st = cols + 4 * HP;       // 2 x (mean, M2) x HP: the two row halves of the tile
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, mt = w & 1, nt = w >> 1;
+    const int KP = (H + 1) & ~1;
+
+    for (int i = t; i < HP * HP; i += kThreads) {
+        const int j = i / HP, k = i - j * HP;
+        Ws[k * WS + j] = j < H && k < H ? W[(size_t)j * H + k] : 0.f;
+    }
+    if (PRO)
+        for (int i = t; i < HP; i += kThreads) {
+            const bool in = i < H;
+            cols[i] = in ? bn.mean[i] : 0.f;
+            cols[HP + i] = in ? bn.invstd[i] : 0.f;
+            cols[2 * HP + i] = in ? bn.gamma[i] : 0.f;
+            cols[3 * HP + i] = in ? bn.beta[i] : 0.f;
+        }
+    double rn = 0.0, rmean = 0.0, rm2 = 0.0;  // thread t < H: column t over this workgroup's tiles
+    const float *xa = Xs + (mt * 32 + (lane & 31)) * XS + (lane >> 5);
+    const float *wb = Ws + (lane >> 5) * WS + nt * 32 + (lane & 31);
+
+    // the next tile's rows wait in registers while this one is multiplied
+    constexpr int NL = kRows * HP / kThreads;
+    float pre[NL];
+    auto fetch = [&](int tile) {
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+            const int i = t + q * kThreads, r = i / HP, c = i - r * HP;
+            const int row = tile * kRows + r;
+            pre[q] = row < P && c < H ? X[(size_t)row * H + c] : 0.f;
+        }
+    };
+    if ((int)blockIdx.x < tiles) fetch(blockIdx.x);
+
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int row0 = tile * kRows;
+        lds_barrier();  // W and the column constants are visible / the previous tile has been consumed
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+            const int i = t + q * kThreads, r = i / HP, c = i - r * HP;
+            float v = pre[q];
+            if (PRO && row0 + r < P && c < H)
+                v = gelu_f(((v - cols[c]) * cols[HP + c]) * cols[2 * HP + c] + cols[3 * HP + c]);
+            Xs[r * XS + c] = v;
+        }
+        lds_barrier();
+        if (tile + (int)gridDim.x < tiles) fetch(tile + gridDim.x);
+        if (nt < NT) {
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            for (int k = 0; k < KP; k += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[k], wb[k * WS], acc, 0, 0, 0);
+            const int col = nt * 32 + (lane & 31);
+            const int rbase = row0 + mt * 32;
+            float sum = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rbase + acc_row(r, lane);
+                if (row < P) {
+                    if (col < H) Y[(size_t)row * H + col] = acc[r];
+                    sum += acc[r];
+                }
+            }
+            sum += __shfl_xor(sum, 32);
+            int nv = P - rbase;
+            nv = nv < 0 ? 0 : (nv > 32 ? 32 : nv);
+            const float mean = nv > 0 ? sum / (float)nv : 0.f;
+            float m2 = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float d = acc[r] - mean;
+                if (rbase + acc_row(r, lane) < P) m2 += d * d;
+            }
+            m2 += __shfl_xor(m2, 32);
+            if (lane < 32) {
+                st[(mt * 2 + 0) * HP + col] = mean;
+                st[(mt * 2 + 1) * HP + col] = m2;
+            }
+        }
+        lds_barrier();
+        if (t < H) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                int nv = P - (row0 + h * 32);
+                nv = nv < 0 ? 0 : (nv > 32 ? 32 : nv);
+                chan(rn, rmean, rm2, (double)nv, (double)st[(h * 2 + 0) * HP + t], (double)st[(h * 2 + 1) * HP + t]);
+            }
+        }
+    }
+    if (t < H) {
+        double *p = partial + (size_t)blockIdx.x * 3 * H;
+        p[t] = rn;
+        p[H + t] = rmean;
+        p[2 * H + t] = rm2;
+    }
+}
+
+// one wave per column
+__global__ __launch_bounds__(64) void k_res_stats(int P, int H, int nb, const double *__restrict__ partial, float eps,
+                                                  float momentum, float *__restrict__ mean_out, float *__restrict__ invstd_out,
+                                                  float *__restrict__ running_mean, float *__restrict__ running_var) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int chunk = div_up(nb, 64);
+    double n = 0.0, mean = 0.0, m2 = 0.0;
+    for (int b = lane * chunk; b < nb && b < (lane + 1) * chunk; ++b) {
+        const double *p = partial + (size_t)b * 3 * H;
+        chan(n, mean, m2, p[c], p[H + c], p[2 * H + c]);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {  // neighbours merge, the lower lanes' rows first
+        const double on = __shfl_xor(n, o), om = __shfl_xor(mean, o), o2 = __shfl_xor(m2, o);
+        if (lane & o) {
+            double an = on, am = om, a2 = o2;
+            chan(an, am, a2, n, mean, m2);
+            n = an; mean = am; m2 = a2;
+        } else {
+            chan(n, mean, m2, on, om, o2);
+        }
+    }
+    if (lane != 0) return;
+    const double var = m2 / (double)P;
+    mean_out[c] = (float)mean;
+    invstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (running_mean) running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mean;
+    if (running_var) running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)(m2 / (double)(P - 1));
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kEwThreads) void k_res_out(size_t n, int H, const float *__restrict__ y2,
+                                                        const float *__restrict__ x, BnCols bn, float *__restrict__ out) {
+    const size_t stride = (size_t)gridDim.x * kEwThreads;
+    for (size_t i = (size_t)blockIdx.x * kEwThreads + threadIdx.x; i < n; i += stride) {
+        if (VEC) {
+            const int c = (int)((i * 4) % (size_t)H);
+            const float4 y = ((const float4 *)y2)[i], xi = ((const float4 *)x)[i];
+            const float4 m = *(const float4 *)(bn.mean + c), is = *(const float4 *)(bn.invstd + c);
+            const float4 g = *(const float4 *)(bn.gamma + c), b = *(const float4 *)(bn.beta + c);
+            float4 o;
+            o.x = gelu_f((((y.x - m.x) * is.x) * g.x + b.x) + xi.x);
+            o.y = gelu_f((((y.y - m.y) * is.y) * g.y + b.y) + xi.y);
+            o.z = gelu_f((((y.z - m.z) * is.z) * g.z + b.z) + xi.z);
+            o.w = gelu_f((((y.w - m.w) * is.w) * g.w + b.w) + xi.w);
+            ((float4 *)out)[i] = o;
+        } else {
+            const int c = (int)(i % (size_t)H);
+            out[i] = gelu_f((((y2[i] - bn.mean[c]) * bn.invstd[c]) * bn.gamma[c] + bn.beta[c]) + x[i]);
+        }
+    }
+}
+
+// CW: power of two >= H, at most 128; thread t takes column t & (CW - 1) and rows t / CW, + 256 / CW, ...
+__global__ __launch_bounds__(kEwThreads) void k_res_bwd_out(int P, int H, int tiles, int CW, const float *__restrict__ g_out,
+                                                            const float *__restrict__ y2, const float *__restrict__ x,
+                                                            BnCols bn, float *__restrict__ g_s, double *__restrict__ partial) {
+    __shared__ double s_red[2][kEwThreads];
+    const int t = threadIdx.x, c = t & (CW - 1), rl = t / CW, RW = kEwThreads / CW;
+    const bool in = c < H;
+    const float m = in ? bn.mean[c] : 0.f, is = in ? bn.invstd[c] : 0.f, g = in ? bn.gamma[c] : 0.f, b = in ? bn.beta[c] : 0.f;
+    double s0 = 0.0, s1 = 0.0;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int row0 = tile * kRows;
+        for (int r = rl; r < kRows; r += RW) {
+            const int row = row0 + r;
+            if (row < P && in) {
+                const size_t i = (size_t)row * H + c;
+                const float xh = (y2[i] - m) * is;
+                const float gs = g_out[i] * gelu_grad((xh * g + b) + x[i]);
+                g_s[i] = gs;
+                s0 += (double)gs;
+                s1 += (double)(gs * xh);
+            }
+        }
+    }
+    s_red[0][t] = s0;
+    s_red[1][t] = s1;
+    lds_barrier();
+    if (t < CW && in) {
+        double a0 = 0.0, a1 = 0.0;
+        for (int q = 0; q < RW; ++q) {
+            a0 += s_red[0][q * CW + t];
+            a1 += s_red[1][q * CW + t];
+        }
+        partial[((size_t)blockIdx.x * 2 + 0) * H + t] = a0;
+        partial[((size_t)blockIdx.x * 2 + 1) * H + t] = a1;
+    }
+}
+
+// one wave per column: sums[c] = sum_b partial[b][0][c], sums[H + c] = sum_b partial[b][1][c], in a fixed order
+__global__ __launch_bounds__(64) void k_res_colsum(int H, int nb, const double *__restrict__ partial, float *__restrict__ sums,
+                                                   float *__restrict__ dbeta, float *__restrict__ dgamma) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    double a0 = 0.0, a1 = 0.0;
+    for (int b = lane; b < nb; b += 64) {
+        a0 += partial[((size_t)b * 2 + 0) * H + c];
+        a1 += partial[((size_t)b * 2 + 1) * H + c];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a0 += __shfl_xor(a0, o);
+        a1 += __shfl_xor(a1, o);
+    }
+    if (lane != 0) return;
+    sums[c] = (float)a0;
+    sums[H + c] = (float)a1;
+    if (dbeta) dbeta[c] = (float)a0;
+    if (dgamma) dgamma[c] = (float)a1;
+}
+
+// STAGE 2: g_in = g_s, yn = y2 (bn2), A = gelu(bn1(y1)), W = W2, g_out = g_z1 (+ column sums for bn1)
+// STAGE 1: g_in = g_z1, yn = y1 (bn1), A = x, W = W1, g_out = g_x = G W1 + g_s
+// g_out == NULL: G W is not computed; partialW == NULL: dW is not computed.
+template <int NT, int STAGE>
+__global__ __launch_bounds__(kThreads) void k_res_bwd_gemm(int P, int H, int tiles, const float *__restrict__ g_in,
+                                                           const float *__restrict__ yn, BnCols bnG,
+                                                           const float *__restrict__ sums, const float *__restrict__ a_in,
+                                                           BnCols bnA, const float *__restrict__ W,
+                                                           const float *__restrict__ g_s, float *__restrict__ g_out,
+                                                           float *__restrict__ partialW, double *__restrict__ partialS) {
+    extern __shared__ __attribute__((aligned(16))) float s_lds[];
+    constexpr int HP = NT * 32, XS = HP + 1, WS = HP + 1;
+    constexpr int NQ = (NT * NT + 7) / 8;  // 32 x 32 tiles of dW per wave
+    float *Gs = s_lds;                // kRows * XS (+ 1: an even float count, As stays 8-byte aligned)
+    float *As = Gs + kRows * XS + (kRows * XS & 1);
+    float *colsG = As + kRows * XS;   // 5 * HP: mean, invstd, gamma invstd, dbeta / P, dgamma / P
+    float *colsA = colsG + 5 * HP;    // 4 * HP: mean, invstd, gamma, beta of bn1 (stage 2)
+    float *Wn = colsA + 4 * HP;       // HP * WS, as stored: Wn[j][k] = W[j][k]
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, mt = w & 1, nt = w >> 1;
+    const int KP = (H + 1) & ~1;
+    const bool want_g = g_out != nullptr, want_w = partialW != nullptr;
+
+    if (want_g)
+        for (int i = t; i < HP * HP; i += kThreads) {
+            const int j = i / HP, k = i - j * HP;
+            Wn[j * WS + k] = j < H && k < H ? W[(size_t)j * H + k] : 0.f;
+        }
+    for (int i = t; i < HP; i += kThreads) {
+        const bool in = i < H;
+        const float is = in ? bnG.invstd[i] : 0.f;
+        colsG[i] = in ? bnG.mean[i] : 0.f;
+        colsG[HP + i] = is;
+        colsG[2 * HP + i] = in ? bnG.gamma[i] * is : 0.f;
+        colsG[3 * HP + i] = in ? sums[i] / (float)P : 0.f;
+        colsG[4 * HP + i] = in ? sums[H + i] / (float)P : 0.f;
+        if (STAGE == 2) {
+            colsA[i] = in ? bnA.mean[i] : 0.f;
+            colsA[HP + i] = in ? bnA.invstd[i] : 0.f;
+            colsA[2 * HP + i] = in ? bnA.gamma[i] : 0.f;
+            colsA[3 * HP + i] = in ? bnA.beta[i] : 0.f;
+        }
+    }
+    f32x16 dw[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dw[q][r] = 0.f;
+    double ps0 = 0.0, ps1 = 0.0;  // stage 2: this lane's rows of column nt * 32 + (lane & 31)
+
+    // the next tile's rows wait in registers while this one is multiplied
+    constexpr int NL = kRows * HP / kThreads;
+    float pg[NL], py[NL], pa[NL];
+    auto fetch = [&](int tile) {
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+            const int i = t + q * kThreads, r = i / HP, c = i - r * HP;
+            const int row = tile * kRows + r;
+            const bool in = row < P && c < H;
+            const size_t at = (size_t)row * H + c;
+            pg[q] = in ? g_in[at] : 0.f;
+            py[q] = in ? yn[at] : 0.f;
+            pa[q] = in && want_w ? a_in[at] : 0.f;
+        }
+    };
+    if ((int)blockIdx.x < tiles) fetch(blockIdx.x);
+
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int row0 = tile * kRows;
+        lds_barrier();  // W and the column constants are visible / the previous tile has been consumed
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+            const int i = t + q * kThreads, r = i / HP, c = i - r * HP;
+            float gy = 0.f, a = 0.f;
+            if (row0 + r < P && c < H) {
+                const float xh = (py[q] - colsG[c]) * colsG[HP + c];
+                gy = colsG[2 * HP + c] * ((pg[q] - colsG[3 * HP + c]) - xh * colsG[4 * HP + c]);
+                a = pa[q];
+                if (STAGE == 2 && want_w)
+                    a = gelu_f(((a - colsA[c]) * colsA[HP + c]) * colsA[2 * HP + c] + colsA[3 * HP + c]);
+            }
+            Gs[r * XS + c] = gy;
+            As[r * XS + c] = a;
+        }
+        lds_barrier();
+        if (tile + (int)gridDim.x < tiles) fetch(tile + gridDim.x);
+        if (want_w) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int id = w + 8 * q;
+                if (id < NT * NT) {
+                    const float *ga = Gs + (lane >> 5) * XS + (id / NT) * 32 + (lane & 31);
+                    const float *ab = As + (lane >> 5) * XS + (id % NT) * 32 + (lane & 31);
+#pragma unroll 4
+                    for (int k = 0; k < kRows; k += 2)
+                        dw[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[k * XS], ab[k * XS], dw[q], 0, 0, 0);
+                }
+            }
+        }
+        if (want_g && nt < NT) {
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            const float *ga = Gs + (mt * 32 + (lane & 31)) * XS + (lane >> 5);
+            const float *wb = Wn + (lane >> 5) * WS + nt * 32 + (lane & 31);
+            for (int j = 0; j < KP; j += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[j], wb[j * WS], acc, 0, 0, 0);
+            const int col = nt * 32 + (lane & 31);
+            if (col < H) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = row0 + mt * 32 + acc_row(r, lane);
+                    if (row >= P) continue;
+                    const size_t at = (size_t)row * H + col;
+                    if (STAGE == 2) {
+                        const float xh = (a_in[at] - colsA[col]) * colsA[HP + col];
+                        const float gz = acc[r] * gelu_grad(xh * colsA[2 * HP + col] + colsA[3 * HP + col]);
+                        g_out[at] = gz;
+                        ps0 += (double)gz;
+                        ps1 += (double)(gz * xh);
+                    } else {
+                        g_out[at] = acc[r] + g_s[at];
+                    }
+                }
+            }
+        }
+    }
+
+    if (want_w) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int id = w + 8 * q;
+            if (id >= NT * NT) continue;
+            const int k = (id % NT) * 32 + (lane & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int j = (id / NT) * 32 + acc_row(r, lane);
+                if (j < H && k < H) partialW[((size_t)blockIdx.x * H + j) * H + k] = dw[q][r];
+            }
+        }
+    }
+    if (STAGE == 2 && want_g) {
+        double *red = (double *)s_lds;  // 2 row halves x 2 sums x HP, over the G tile
+        ps0 += __shfl_xor(ps0, 32);
+        ps1 += __shfl_xor(ps1, 32);
+        lds_barrier();  // every wave is done with the last tile
+        if (nt < NT && lane < 32) {
+            red[(mt * 2 + 0) * HP + nt * 32 + lane] = ps0;
+            red[(mt * 2 + 1) * HP + nt * 32 + lane] = ps1;
+        }
+        lds_barrier();
+        if (t < H) {
+            partialS[((size_t)blockIdx.x * 2 + 0) * H + t] = red[t] + red[2 * HP + t];
+            partialS[((size_t)blockIdx.x * 2 + 1) * H + t] = red[HP + t] + red[3 * HP + t];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_res_reduce_w(int n, int nb, const float *__restrict__ partial, float *__restrict__ dW) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) s += (double)partial[(size_t)b * n + i];
+    dW[i] = (float)s;
+}
+
+// ---- host launchers --------------------------------------------------------------------------
+namespace {
+int res_nt(int H) { return div_up(H, 32); }
+
+size_t fwd_lds(int nt) {
+    const int HP = nt * 32;
+    return sizeof(float) * ((size_t)kRows * (HP + 1) + (size_t)HP * (HP + 1) + 8 * HP);
+}
+size_t bwd_lds(int nt) {
+    const int HP = nt * 32, tile = kRows * (HP + 1);
+    return sizeof(float) * ((size_t)2 * tile + (tile & 1) + 9 * HP + (size_t)HP * (HP + 1));
+}
+
+template <int NT, bool PRO>
+hipError_t run_gemm(int nb, int P, int H, const float *X, const float *W, const BnCols &bn, float *Y, double *partial,
+                    hipStream_t s) {
+    const size_t lds = fwd_lds(NT);
+    hipError_t e = hipFuncSetAttribute((const void *)k_res_gemm<NT, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    k_res_gemm<NT, PRO><<<nb, kThreads, lds, s>>>(P, H, div_up(P, kRows), X, W, bn, Y, partial);
+    return hipGetLastError();
+}
+
+template <bool PRO>
+hipError_t gemm(int nb, int P, int H, const float *X, const float *W, const BnCols &bn, float *Y, double *partial,
+                hipStream_t s) {
+    switch (res_nt(H)) {
+    case 1: return run_gemm<1, PRO>(nb, P, H, X, W, bn, Y, partial, s);
+    case 2: return run_gemm<2, PRO>(nb, P, H, X, W, bn, Y, partial, s);
+    case 3: return run_gemm<3, PRO>(nb, P, H, X, W, bn, Y, partial, s);
+    default: return run_gemm<4, PRO>(nb, P, H, X, W, bn, Y, partial, s);
+    }
+}
+
+template <int NT, int STAGE>
+hipError_t run_bwd_gemm(int nb, int P, int H, const float *g_in, const float *yn, const BnCols &bnG, const float *sums,
+                        const float *a_in, const BnCols &bnA, const float *W, const float *g_s, float *g_out,
+                        float *partialW, double *partialS, hipStream_t s) {
+    const size_t lds = bwd_lds(NT);
+    hipError_t e = hipFuncSetAttribute((const void *)k_res_bwd_gemm<NT, STAGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    k_res_bwd_gemm<NT, STAGE><<<nb, kThreads, lds, s>>>(P, H, div_up(P, kRows), g_in, yn, bnG, sums, a_in, bnA, W, g_s,
+                                                        g_out, partialW, partialS);
+    return hipGetLastError();
+}
+
+template <int STAGE>
+hipError_t bwd_gemm(int nb, int P, int H, const float *g_in, const float *yn, const BnCols &bnG, const float *sums,
+                    const float *a_in, const BnCols &bnA, const float *W, const float *g_s, float *g_out, float *partialW,
+                    double *partialS, hipStream_t s) {
+    switch (res_nt(H)) {
+    case 1: return run_bwd_gemm<1, STAGE>(nb, P, H, g_in, yn, bnG, sums, a_in, bnA, W, g_s, g_out, partialW, partialS, s);
+    case 2: return run_bwd_gemm<2, STAGE>(nb, P, H, g_in, yn, bnG, sums, a_in, bnA, W, g_s, g_out, partialW, partialS, s);
+    case 3: return run_bwd_gemm<3, STAGE>(nb, P, H, g_in, yn, bnG, sums, a_in, bnA, W, g_s, g_out, partialW, partialS, s);
+    default: return run_bwd_gemm<4, STAGE>(nb, P, H, g_in, yn, bnG, sums, a_in, bnA, W, g_s, g_out, partialW, partialS, s);
+    }
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+}  // namespace
+
+int resblock_blocks(int P, int H, int max_blocks) {
+    const int tiles = div_up(P, kRows);
+    // H <= 64: two workgroups fit a CU's LDS
+    const int cap = max_blocks > 0 ? max_blocks : kResblockAutoBlocks * (H <= 64 ? 2 : 1);
+    return tiles < cap ? tiles : cap;
+}
+
+int resblock_out_blocks(int P, int max_blocks) {
+    const int tiles = div_up(P, kRows);
+    const int cap = max_blocks > 0 ? max_blocks : kOutBlocks;
+    return tiles < cap ? tiles : cap;
+}
+
+ResblockWorkspace::ResblockWorkspace(int P, int H, int max_blocks, bool backward) {
+    const size_t nb = (size_t)resblock_blocks(P, H, max_blocks), no = (size_t)resblock_out_blocks(P, max_blocks);
+    const size_t h = (size_t)H, ph = (size_t)P * h;
+    size_t o = 0;
+    partial_s = o; o = align256(o + sizeof(double) * 3 * h * (nb > no ? nb : no));
+    partial_w = sums = g_s = g_z1 = o;
+    if (backward) {
+        partial_w = o; o = align256(o + sizeof(float) * nb * h * h);
+        sums = o;      o = align256(o + sizeof(float) * 4 * h);
+        g_s = o;       o = align256(o + sizeof(float) * ph);
+        g_z1 = o;      o = align256(o + sizeof(float) * ph);
+    }
+    total = o;
+}
+
+hipError_t launch_resblock_fwd(int P, int H, const float *x, const float *W1, const float *gamma1, const float *beta1,
+                               const float *W2, const float *gamma2, const float *beta2, float eps1, float eps2,
+                               float momentum1, float momentum2, float *running_mean1, float *running_var1,
+                               float *running_mean2, float *running_var2, char *ws, int max_blocks, float *y1, float *y2,
+                               float *out, float *stats, hipStream_t s) {
+    const ResblockWorkspace L(P, H, max_blocks, false);
+    const int nb = resblock_blocks(P, H, max_blocks);
+    double *partial = (double *)(ws + L.partial_s);
+    const BnCols none = {nullptr, nullptr, nullptr, nullptr};
+    const BnCols bn1 = {stats, stats + H, gamma1, beta1}, bn2 = {stats + 2 * H, stats + 3 * H, gamma2, beta2};
+    hipError_t e = gemm<false>(nb, P, H, x, W1, none, y1, partial, s);
+    if (e != hipSuccess) return e;
+    k_res_stats<<<H, 64, 0, s>>>(P, H, nb, partial, eps1, momentum1, stats, stats + H, running_mean1, running_var1);
+    e = gemm<true>(nb, P, H, y1, W2, bn1, y2, partial, s);
+    if (e != hipSuccess) return e;
+    k_res_stats<<<H, 64, 0, s>>>(P, H, nb, partial, eps2, momentum2, stats + 2 * H, stats + 3 * H, running_mean2, running_var2);
+    const size_t n = (size_t)P * H;
+    const bool vec = H % 4 == 0 && aligned16(y2) && aligned16(x) && aligned16(out) && aligned16(stats) &&
+                     aligned16(gamma2) && aligned16(beta2);
+    const size_t items = vec ? n / 4 : n;
+    const size_t want = (items + kEwThreads - 1) / kEwThreads;
+    const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
+    if (vec) k_res_out<true><<<grid, kEwThreads, 0, s>>>(items, H, y2, x, bn2, out);
+    else k_res_out<false><<<grid, kEwThreads, 0, s>>>(items, H, y2, x, bn2, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_resblock_bwd(int P, int H, const float *x, const float *y1, const float *y2, const float *stats,
+                               const float *W1, const float *gamma1, const float *beta1, const float *W2,
+                               const float *gamma2, const float *beta2, const float *g_out, char *ws, int max_blocks,
+                               float *dx, float *dW1, float *dgamma1, float *dbeta1, float *dW2, float *dgamma2,
+                               float *dbeta2, hipStream_t s) {
+    const ResblockWorkspace L(P, H, max_blocks, true);
+    const int nb = resblock_blocks(P, H, max_blocks), no = resblock_out_blocks(P, max_blocks), tiles = div_up(P, kRows);
+    double *partial_s = (double *)(ws + L.partial_s);
+    float *partial_w = (float *)(ws + L.partial_w), *sums = (float *)(ws + L.sums);
+    float *g_s = (float *)(ws + L.g_s), *g_z1 = (float *)(ws + L.g_z1);
+    const BnCols bn1 = {stats, stats + H, gamma1, beta1}, bn2 = {stats + 2 * H, stats + 3 * H, gamma2, beta2};
+    const bool below = dx || dW1 || dgamma1 || dbeta1;  // anything past a1
+    int CW = 8;
+    while (CW < H) CW <<= 1;
+    k_res_bwd_out<<<no, kEwThreads, 0, s>>>(P, H, tiles, CW, g_out, y2, x, bn2, g_s, partial_s);
+    k_res_colsum<<<H, 64, 0, s>>>(H, no, partial_s, sums, dbeta2, dgamma2);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (dW2 || below) {
+        e = bwd_gemm<2>(nb, P, H, g_s, y2, bn2, sums, y1, bn1, W2, nullptr, below ? g_z1 : nullptr,
+                        dW2 ? partial_w : nullptr, partial_s, s);
+        if (e != hipSuccess) return e;
+        if (dW2) k_res_reduce_w<<<div_up(H * H, 256), 256, 0, s>>>(H * H, nb, partial_w, dW2);
+        if (below) k_res_colsum<<<H, 64, 0, s>>>(H, nb, partial_s, sums + 2 * H, dbeta1, dgamma1);
+    }
+    if (dx || dW1) {
+        e = bwd_gemm<1>(nb, P, H, g_z1, y1, bn1, sums + 2 * H, x, bn1, W1, g_s, dx, dW1 ? partial_w : nullptr, nullptr, s);
+        if (e != hipSuccess) return e;
+        if (dW1) k_res_reduce_w<<<div_up(H * H, 256), 256, 0, s>>>(H * H, nb, partial_w, dW1);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace gsr

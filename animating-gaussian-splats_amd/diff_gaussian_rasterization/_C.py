@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = (
     "gsr_spec_keys", "gsr_async_shutdown", "gsr_debug_async_fault", "gsr_set_exact_thresholds",
     "gsr_knn", "gsr_rigidity_scratch_bytes", "gsr_rigidity_forward", "gsr_rigidity_backward",
     "gsr_posenc_ranges", "gsr_posenc_forward", "gsr_deform_in_forward", "gsr_deform_in_workspace_bytes",
-    "gsr_deform_in_backward",
+    "gsr_deform_in_backward", "gsr_resblock_workspace_bytes", "gsr_resblock_forward", "gsr_resblock_backward",
 )
 
 
@@ -206,6 +206,17 @@ def load_library():
         _DEFORM_MISSING = None
     except AttributeError as err:
         _DEFORM_MISSING = str(err)
+    global _RESBLOCK_MISSING
+    try:  # likewise additive to ABI 21
+        L.gsr_resblock_workspace_bytes.restype = ctypes.c_size_t
+        L.gsr_resblock_workspace_bytes.argtypes = [i, i, i, i]
+        L.gsr_resblock_forward.restype = i
+        L.gsr_resblock_forward.argtypes = [i, i] + [vp] * 7 + [f] * 4 + [vp] * 5 + [i] + [vp] * 5
+        L.gsr_resblock_backward.restype = i
+        L.gsr_resblock_backward.argtypes = [i, i] + [vp] * 12 + [i] + [vp] * 8
+        _RESBLOCK_MISSING = None
+    except AttributeError as err:
+        _RESBLOCK_MISSING = str(err)
     if L.gsr_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libgsr.so ABI {L.gsr_abi_version()} != binding ABI {ABI_VERSION}: rebuild it")
     global _PREALLOC_FN
@@ -226,6 +237,19 @@ def deform_library():
     L = load_library()
     if _DEFORM_MISSING is not None:
         raise RuntimeError(f"libgsr.so at {LIB_PATH} lacks the deformation input layer ({_DEFORM_MISSING}): "
+                           "rebuild it with `make -C animating-gaussian-splats_amd/csrc`")
+    return L
+
+
+_RESBLOCK_MISSING = None  # likewise for the fused residual blocks' entry points
+
+
+def resblock_library():
+    """The library, for the fused residual blocks (splat_deform.residual_block): raises when
+    ``libgsr.so`` predates their entry points, on first use of the feature only."""
+    L = load_library()
+    if _RESBLOCK_MISSING is not None:
+        raise RuntimeError(f"libgsr.so at {LIB_PATH} lacks the fused residual blocks ({_RESBLOCK_MISSING}): "
                            "rebuild it with `make -C animating-gaussian-splats_amd/csrc`")
     return L
 

@@ -1,4 +1,5 @@
-"""The deformation network of train.py with its input side on the HIP kernels of ``libgsr.so``.
+"""The deformation network of train.py with its input side and its residual blocks on the HIP kernels
+of ``libgsr.so``.
 
 Every step the reference re-encodes the previous cloud (``normalize_and_encode_means_and_rotations``,
 train.py:185-204), repeats the progress encoding over all rows, ``torch.cat``s both with the initial
@@ -10,8 +11,11 @@ Gaussian (csrc/gsr_deform.hip), and its backward recomputes the features for ``d
 * ``deform_input_layer(weight, bias, initial_params, previous_params, progress)`` -- ``fc_in`` applied
   to ``[enc(initial) | enc(previous) | enc(progress)]``; gradients flow to ``weight`` and ``bias`` only
   (the reference detaches the encoded parameters, train.py:255-258);
-* ``DeformationNetwork`` -- train.py:80-110 with the reference's ``state_dict`` names and shapes; the
-  residual blocks (training-mode BatchNorm over all rows, H x H GEMMs) and ``fc_out`` stay torch;
+* ``residual_block(x, fc1_weight, bn1, fc2_weight, bn2)`` -- one ResidualBlock (train.py:57-77) with
+  training-mode BatchNorm, fused (csrc/gsr_resblock.hip): three (P, H) tensors stay alive for the backward;
+  ``set_fused_residual_blocks(False)`` sends ``ResidualBlock`` back to the torch ops;
+* ``DeformationNetwork`` -- train.py:80-110 with the reference's ``state_dict`` names and shapes; its
+  residual blocks run fused when eligible (training mode, H <= 128), ``fc_out`` stays torch;
 * ``update_gaussian_cloud_parameters`` -- train.py:269-308.
 
 All fp32.  There is no CPU path: CPU tensors raise.
@@ -23,10 +27,12 @@ from torch import nn
 
 from diff_gaussian_rasterization import _C
 
-__all__ = ["encode_means_and_rotations", "encoding_ranges", "deform_input_layer", "ResidualBlock",
-           "DeformationNetwork", "update_gaussian_cloud_parameters", "MAX_HIDDEN"]
+__all__ = ["encode_means_and_rotations", "encoding_ranges", "deform_input_layer", "residual_block",
+           "set_fused_residual_blocks", "ResidualBlock", "DeformationNetwork", "update_gaussian_cloud_parameters",
+           "MAX_HIDDEN", "MAX_FUSED_HIDDEN"]
 
 MAX_HIDDEN = 512
+MAX_FUSED_HIDDEN = 128  # widest hidden dimension of the fused residual blocks (wider ones run the torch ops)
 ENCODING_WIDTH = 92  # 3 means x 10 frequencies x (sin, cos) + 4 quaternion components x 4 x 2
 INPUT_WIDTH = 192    # two encodings + the 8 progress columns
 RANGE_BLOCKS = 256   # GSR_POSENC_RANGE_BLOCKS of include/gsr.h
@@ -150,8 +156,105 @@ def deform_input_layer(weight, bias, initial_params, previous_params, progress, 
     return _DeformIn.apply(weight, bias, im, iq, ir, pm, pq, pr, progress, int(max_blocks), save)
 
 
+_FUSED_RESBLOCKS = True
+
+
+def set_fused_residual_blocks(on):
+    """Whether ``ResidualBlock.forward`` runs eligible calls on the fused kernels (default) or always on
+    the torch ops (the A/B switch of tools/bench_resblock.py).  Process-wide; returns the previous setting."""
+    global _FUSED_RESBLOCKS
+    previous, _FUSED_RESBLOCKS = _FUSED_RESBLOCKS, bool(on)
+    return previous
+
+
+class _ResBlock(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, g1, b1, w2, g2, b2, bn1, bn2, max_blocks, save):
+        L = _C.resblock_library()
+        P, H, dev = x.shape[0], x.shape[1], x.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731 - every element is written
+        y1, y2, out, stats = new(P, H), new(P, H), new(P, H), new(4 * H)
+        ws = torch.empty(max(L.gsr_resblock_workspace_bytes(P, H, max_blocks, 0), 1), dtype=torch.uint8, device=dev)
+        running = [t.data_ptr() if t is not None else None
+                   for t in (bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var)]
+        with _C._device_guard(dev):
+            _C._check(L.gsr_resblock_forward(P, H, x.data_ptr(), w1.data_ptr(), g1.data_ptr(), b1.data_ptr(),
+                                             w2.data_ptr(), g2.data_ptr(), b2.data_ptr(), bn1.eps, bn2.eps,
+                                             bn1.momentum, bn2.momentum, *running, ws.data_ptr(), max_blocks,
+                                             y1.data_ptr(), y2.data_ptr(), out.data_ptr(), stats.data_ptr(),
+                                             _C._stream_ptr(dev)))
+        if save:
+            ctx.save_for_backward(x, y1, y2, stats, w1, g1, b1, w2, g2, b2)
+            ctx.max_blocks = max_blocks
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        L = _C.resblock_library()
+        x, y1, y2, stats, w1, g1, b1, w2, g2, b2 = ctx.saved_tensors
+        P, H, dev = x.shape[0], x.shape[1], x.device
+        g = g.contiguous().float()
+        grads = [torch.empty_like(t) if need else None
+                 for t, need in zip((x, w1, g1, b1, w2, g2, b2), ctx.needs_input_grad[:7])]
+        ws = torch.empty(max(L.gsr_resblock_workspace_bytes(P, H, ctx.max_blocks, 1), 1), dtype=torch.uint8, device=dev)
+        with _C._device_guard(dev):
+            _C._check(L.gsr_resblock_backward(P, H, x.data_ptr(), y1.data_ptr(), y2.data_ptr(), stats.data_ptr(),
+                                              w1.data_ptr(), g1.data_ptr(), b1.data_ptr(), w2.data_ptr(), g2.data_ptr(),
+                                              b2.data_ptr(), g.data_ptr(), ws.data_ptr(), ctx.max_blocks,
+                                              *[t.data_ptr() if t is not None else None for t in grads],
+                                              _C._stream_ptr(dev)))
+        return tuple(grads) + (None,) * 4
+
+
+def _check_bn(bn, H, name):
+    if not isinstance(bn, nn.BatchNorm1d) or bn.num_features != H:
+        raise ValueError(f"residual_block: {name} must be a BatchNorm1d over {H} features")
+    if not bn.affine or bn.momentum is None:
+        raise ValueError(f"residual_block: {name} must be affine with a momentum (no cumulative average)")
+    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"residual_block: {name} must hold contiguous float32 tensors")
+
+
+def residual_block(x, fc1_weight, bn1, fc2_weight, bn2, max_blocks=0):
+    """One ResidualBlock of train.py:57-77 on the kernels of csrc/gsr_resblock.hip:
+    ``gelu(bn2(gelu(bn1(x @ fc1_weight.T)) @ fc2_weight.T) + x)`` for ``x`` (P >= 2, H <= 128) float32 on
+    the GPU, ``fc*_weight`` (H, H) and ``bn*`` the two ``nn.BatchNorm1d`` modules, always normalising with
+    the batch statistics (training mode).  Their running statistics are blended and
+    ``num_batches_tracked`` incremented as ``F.batch_norm`` does.  Gradients flow to ``x``, both weights and
+    both BatchNorms' affine parameters; the graph keeps ``x``, the two GEMM outputs and 4 H statistics.
+    ``max_blocks``: upper bound on the persistent workgroups (0: automatic)."""
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"residual_block: x {tuple(x.shape)} {x.dtype}, expected float32 (P, H)")
+    P, H = x.shape
+    if not 1 <= H <= MAX_FUSED_HIDDEN:
+        raise ValueError(f"residual_block: hidden dimension {H} outside [1, {MAX_FUSED_HIDDEN}]")
+    if P < 2:
+        raise ValueError(f"residual_block: batch statistics need more than one row (got {P})")
+    for w, name in ((fc1_weight, "fc1_weight"), (fc2_weight, "fc2_weight")):
+        if tuple(w.shape) != (H, H) or w.dtype != torch.float32:
+            raise ValueError(f"residual_block: {name} {tuple(w.shape)} {w.dtype}, expected float32 ({H}, {H})")
+    _check_bn(bn1, H, "bn1")
+    _check_bn(bn2, H, "bn2")
+    if max_blocks < 0:
+        raise ValueError("residual_block: max_blocks must be >= 0")
+    params = (fc1_weight, bn1.weight, bn1.bias, fc2_weight, bn2.weight, bn2.bias)
+    _need_gpu("x, the weights and the BatchNorms", x, *params,
+              *(t for bn in (bn1, bn2) for t in (bn.running_mean, bn.running_var) if t is not None))
+    save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+    out = _ResBlock.apply(x.contiguous(), fc1_weight.contiguous(), bn1.weight, bn1.bias, fc2_weight.contiguous(),
+                          bn2.weight, bn2.bias, bn1, bn2, int(max_blocks), save)
+    with torch.no_grad():
+        for bn in (bn1, bn2):
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked += 1
+    return out
+
+
 class ResidualBlock(nn.Module):
-    """train.py:57-77."""
+    """train.py:57-77.  A training-mode call on a contiguous float32 GPU (P >= 2, H <= 128) input runs
+    ``residual_block`` (unless ``set_fused_residual_blocks(False)``); every other call the torch ops."""
 
     def __init__(self, dimension):
         super().__init__()
@@ -160,7 +263,23 @@ class ResidualBlock(nn.Module):
         self.fc2 = nn.Linear(dimension, dimension, bias=False)
         self.bn2 = nn.BatchNorm1d(dimension)
 
+    def _fused(self, x):
+        if not (_FUSED_RESBLOCKS and self.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+                and x.is_contiguous() and x.shape[0] >= 2 and x.shape[1] <= MAX_FUSED_HIDDEN):
+            return False
+        if tuple(self.fc1.weight.shape) != (x.shape[1],) * 2 or tuple(self.fc2.weight.shape) != (x.shape[1],) * 2:
+            return False
+        for bn in (self.bn1, self.bn2):
+            if not (isinstance(bn, nn.BatchNorm1d) and bn.affine and bn.track_running_stats and bn.momentum is not None
+                    and bn.running_mean is not None):
+                return False
+        return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (
+            self.fc1.weight, self.fc2.weight, self.bn1.weight, self.bn1.bias, self.bn2.weight, self.bn2.bias,
+            self.bn1.running_mean, self.bn1.running_var, self.bn2.running_mean, self.bn2.running_var))
+
     def forward(self, x):
+        if self._fused(x):
+            return residual_block(x, self.fc1.weight, self.bn1, self.fc2.weight, self.bn2)
         identity = x
         x = nn.functional.gelu(self.bn1(self.fc1(x)))
         x = self.bn2(self.fc2(x))

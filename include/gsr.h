@@ -438,6 +438,35 @@ int gsr_deform_in_backward(int P, int H, const float *initial_means, const float
                            const float *dL_dout, void *workspace, int max_blocks, float *dL_dweight,
                            float *dL_dbias, void *stream);
 
+/* ---- Deformation network residual blocks (additive to ABI 21) -----------------------------------
+ * One ResidualBlock of train.py:57-77 on x (P, H) fp32 row-major, 2 <= P, 1 <= H <= 128:
+ *     y1 = x fc1_weight^T;  a1 = gelu(bn1(y1));  y2 = a1 fc2_weight^T;  out = gelu(bn2(y2) + x)
+ * fc*_weight (H, H) as in nn.Linear(H, H, bias=False); bn* in training mode: normalised with the batch
+ * mean and the biased batch variance (Chan's formula in double over per-workgroup (count, mean, M2)
+ * partials), affine with bn*_weight / bn*_bias (H); GELU in the exact erf form.  The running-statistic
+ * arrays (H each, may be NULL) are blended in place as (1 - momentum) old + momentum new, the variance
+ * unbiased (P / (P - 1)), which is torch's rule.  The forward writes y1, y2, out (P, H each) and stats
+ * (4 H: mean1, invstd1, mean2, invstd2 with invstd = 1 / sqrt(var + eps)); x, y1, y2 and stats are what
+ * the backward needs.  The backward writes the gradients whose pointers are not NULL (dL_dx (P, H),
+ * dL_dfc*_weight (H, H), dL_dbn*_weight / _bias (H)); the others are not computed.  workspace:
+ * gsr_resblock_workspace_bytes(P, H, max_blocks, backward) bytes of device memory (the backward's holds
+ * two transient (P, H) gradients), not kept between the two calls.  max_blocks > 0: at most that many
+ * persistent workgroups (0: automatic).  No float atomics: every row reduction is one partial per
+ * workgroup summed in workgroup order, two runs are bitwise equal. */
+size_t gsr_resblock_workspace_bytes(int P, int H, int max_blocks, int backward);
+int gsr_resblock_forward(int P, int H, const float *x, const float *fc1_weight, const float *bn1_weight,
+                         const float *bn1_bias, const float *fc2_weight, const float *bn2_weight,
+                         const float *bn2_bias, float eps1, float eps2, float momentum1, float momentum2,
+                         float *bn1_running_mean, float *bn1_running_var, float *bn2_running_mean,
+                         float *bn2_running_var, void *workspace, int max_blocks, float *y1, float *y2, float *out,
+                         float *stats, void *stream);
+int gsr_resblock_backward(int P, int H, const float *x, const float *y1, const float *y2, const float *stats,
+                          const float *fc1_weight, const float *bn1_weight, const float *bn1_bias,
+                          const float *fc2_weight, const float *bn2_weight, const float *bn2_bias,
+                          const float *dL_dout, void *workspace, int max_blocks, float *dL_dx, float *dL_dfc1_weight,
+                          float *dL_dbn1_weight, float *dL_dbn1_bias, float *dL_dfc2_weight, float *dL_dbn2_weight,
+                          float *dL_dbn2_bias, void *stream);
+
 /* ---- Densification: statistics, clone / split / prune with Adam state surgery (ABI >= 4) ------
  * SURVEY.md 8(f) row 2.  Replaces update_max_2d_radii_and_visibility_mask (densify.py:154-162),
  * accumulate_mean_2d_gradients (external.py:113-124) and the body of densify_gaussians
@@ -530,7 +559,7 @@ int gsr_views_pack(int frames, int H, int W, const uint8_t *rgb, const uint8_t *
 /* Per-phase device timing with HIP events recorded on the call's stream (off by default).
  * Phases: "preprocess", "bin_count", "bin_scan", "bin_emit", "tile_sort", "render_fwd",
  * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "knn", "rigidity_fwd", "rigidity_bwd",
- * "posenc_ranges", "posenc", "deform_in_fwd", "deform_in_bwd".  gsr_profile_read synchronises on the recorded events. */
+ * "posenc_ranges", "posenc", "deform_in_fwd", "deform_in_bwd", "resblock_fwd", "resblock_bwd".  gsr_profile_read synchronises on the recorded events. */
 int gsr_profile_enable(int on);
 /* Restrict event recording to a comma-separated list of phases (NULL or "" = every phase), so a
  * timed region can carry the events of one kernel only.  Host-side timers are unaffected. */
