@@ -1,8 +1,8 @@
 // gsr_api_aux.hip -- C ABI of libgsr (declared in include/gsr.h): the entry points beside the
 // rasterizer -- fused L1 + SSIM, k-nearest neighbours and the rigidity loss, the deformation network's
-// input layer and residual blocks, densification, fused Adam and the camera-frame packing.  Argument
-// validation and workspace carving; the kernels are in gsr_loss.hip, gsr_rigidity.hip, gsr_deform.hip,
-// gsr_resblock.hip, gsr_densify.hip, gsr_adam.hip and gsr_io.hip.
+// input layer, residual blocks and output head, densification, fused Adam and the camera-frame packing.
+// Argument validation and workspace carving; the kernels are in gsr_loss.hip, gsr_rigidity.hip, gsr_deform.hip,
+// gsr_resblock.hip, gsr_head.hip, gsr_densify.hip, gsr_adam.hip and gsr_io.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -80,6 +80,13 @@ int check_resblock(int P, int H, int max_blocks) {
     if (H < 1 || H > kResblockMaxH)
         return fail(GSR_ERR_ARG, "resblock: hidden dimension %d (1 to %d supported)", H, kResblockMaxH);
     if (max_blocks < 0) return fail(GSR_ERR_ARG, "resblock: max_blocks must be >= 0 (0: automatic)");
+    return GSR_OK;
+}
+
+int check_head(int P, int H) {
+    if (P < 0) return fail(GSR_ERR_ARG, "deform_out: P must be >= 0");
+    if (H < 1 || H > kHeadMaxH)
+        return fail(GSR_ERR_UNSUPPORTED, "deform_out: hidden dimension %d (1 to %d supported)", H, kHeadMaxH);
     return GSR_OK;
 }
 
@@ -307,6 +314,45 @@ int gsr_resblock_backward(int P, int H, const float *x, const float *y1, const f
     HIP_TRY(launch_resblock_bwd(P, H, x, y1, y2, stats, fc1_weight, bn1_weight, bn1_bias, fc2_weight, bn2_weight,
                                 bn2_bias, dL_dout, (char *)workspace, max_blocks, dL_dx, dL_dfc1_weight, dL_dbn1_weight,
                                 dL_dbn1_bias, dL_dfc2_weight, dL_dbn2_weight, dL_dbn2_bias, s));
+    return GSR_OK;
+}
+
+// ---- deformation network output head ----------------------------------------------------------
+int gsr_deform_out_forward(int P, int H, const float *x, const float *weight, const float *bias,
+                           const float *initial_means, const float *initial_rotation_quaternions, float *out,
+                           void *stream) {
+    int rc = check_head(P, H);
+    if (rc) return rc;
+    if (P == 0) return GSR_OK;
+    if (!x || !weight || !bias || !initial_means || !initial_rotation_quaternions || !out)
+        return fail(GSR_ERR_ARG, "deform_out: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "deform_out_fwd");
+    HIP_TRY(launch_head_fwd(P, H, x, weight, bias, initial_means, initial_rotation_quaternions, out, s));
+    return GSR_OK;
+}
+
+size_t gsr_deform_out_workspace_bytes(int P, int H, int max_blocks) {
+    if (P <= 0 || H < 1 || H > kHeadMaxH || max_blocks < 0) return 0;
+    return align256(sizeof(float) * head_partial_floats(P, H, max_blocks));
+}
+
+int gsr_deform_out_backward(int P, int H, const float *x, const float *weight, const float *dL_dout, void *workspace,
+                            int max_blocks, float *dL_dx, float *dL_dweight, float *dL_dbias, void *stream) {
+    int rc = check_head(P, H);
+    if (rc) return rc;
+    if (max_blocks < 0) return fail(GSR_ERR_ARG, "deform_out: max_blocks must be >= 0 (0: automatic)");
+    if (!dL_dx && !dL_dweight && !dL_dbias) return GSR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0) {  // empty sums: no kernel
+        if (dL_dweight) HIP_TRY(hipMemsetAsync(dL_dweight, 0, sizeof(float) * 7 * (size_t)H, s));
+        if (dL_dbias) HIP_TRY(hipMemsetAsync(dL_dbias, 0, sizeof(float) * 7, s));
+        return GSR_OK;
+    }
+    if (!dL_dout || (dL_dx && !weight) || (dL_dweight && !x) || ((dL_dweight || dL_dbias) && !workspace))
+        return fail(GSR_ERR_ARG, "deform_out: null pointer");
+    Phase ph(s, "deform_out_bwd");
+    HIP_TRY(launch_head_bwd(P, H, x, weight, dL_dout, (float *)workspace, max_blocks, dL_dx, dL_dweight, dL_dbias, s));
     return GSR_OK;
 }
 

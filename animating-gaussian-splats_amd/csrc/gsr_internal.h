@@ -170,6 +170,17 @@ hipError_t launch_resblock_bwd(int P, int H, const float *x, const float *y1, co
                                float *dx, float *dW1, float *dgamma1, float *dbeta1, float *dW2, float *dgamma2,
                                float *dbeta2, hipStream_t s);
 
+// deformation network output head (gsr_head.hip): fc_out and the "+ initial" update; im / iq the initial
+// means (P, 3) and quaternions (P, 4)
+constexpr int kHeadAutoBlocks = 1024;  // persistent backward workgroups when the caller sets no bound (four per CU)
+constexpr int kHeadMaxH = 512;
+hipError_t launch_head_fwd(int P, int H, const float *x, const float *W, const float *bias, const float *im,
+                           const float *iq, float *out, hipStream_t s);
+int head_blocks(int P, int max_blocks);
+size_t head_partial_floats(int P, int H, int max_blocks);
+hipError_t launch_head_bwd(int P, int H, const float *x, const float *W, const float *g, float *partial, int max_blocks,
+                           float *dx, float *dW, float *db, hipStream_t s);
+
 // densification (gsr_densify.hip)
 struct DensArgs {
     int P, prune_big;

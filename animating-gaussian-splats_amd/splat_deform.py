@@ -1,5 +1,5 @@
-"""The deformation network of train.py with its input side and its residual blocks on the HIP kernels
-of ``libgsr.so``.
+"""The deformation network of train.py with its input side, its residual blocks and its output head on the
+HIP kernels of ``libgsr.so``.
 
 Every step the reference re-encodes the previous cloud (``normalize_and_encode_means_and_rotations``,
 train.py:185-204), repeats the progress encoding over all rows, ``torch.cat``s both with the initial
@@ -14,9 +14,13 @@ Gaussian (csrc/gsr_deform.hip), and its backward recomputes the features for ``d
 * ``residual_block(x, fc1_weight, bn1, fc2_weight, bn2)`` -- one ResidualBlock (train.py:57-77) with
   training-mode BatchNorm, fused (csrc/gsr_resblock.hip): three (P, H) tensors stay alive for the backward;
   ``set_fused_residual_blocks(False)`` sends ``ResidualBlock`` back to the torch ops;
+* ``deform_output_layer(x, weight, bias, initial_params)`` -- ``fc_out`` and the ``+ [initial means | initial
+  quaternions]`` that follows it (train.py:106-108) in one kernel (csrc/gsr_head.hip), the (P, 7) concatenation
+  never built; gradients flow to ``x``, ``weight`` and ``bias`` (and to the initial values if they require one);
+  ``set_fused_output_head(False)`` sends ``DeformationNetwork`` back to the two torch lines;
 * ``DeformationNetwork`` -- train.py:80-110 with the reference's ``state_dict`` names and shapes; its
-  residual blocks run fused when eligible (training mode, H <= 128), ``fc_out`` stays torch;
-* ``update_gaussian_cloud_parameters`` -- train.py:269-308.
+  residual blocks run fused when eligible (training mode, H <= 128), its output head in either mode;
+* ``update_gaussian_cloud_parameters`` -- train.py:269-308; the ``* 0.01`` update stays in torch.
 
 All fp32.  There is no CPU path: CPU tensors raise.
 """
@@ -28,8 +32,8 @@ from torch import nn
 from diff_gaussian_rasterization import _C
 
 __all__ = ["encode_means_and_rotations", "encoding_ranges", "deform_input_layer", "residual_block",
-           "set_fused_residual_blocks", "ResidualBlock", "DeformationNetwork", "update_gaussian_cloud_parameters",
-           "MAX_HIDDEN", "MAX_FUSED_HIDDEN"]
+           "set_fused_residual_blocks", "deform_output_layer", "set_fused_output_head", "ResidualBlock",
+           "DeformationNetwork", "update_gaussian_cloud_parameters", "MAX_HIDDEN", "MAX_FUSED_HIDDEN"]
 
 MAX_HIDDEN = 512
 MAX_FUSED_HIDDEN = 128  # widest hidden dimension of the fused residual blocks (wider ones run the torch ops)
@@ -287,10 +291,98 @@ class ResidualBlock(nn.Module):
         return nn.functional.gelu(x)
 
 
+_FUSED_HEAD = True
+
+
+def set_fused_output_head(on):
+    """Whether ``DeformationNetwork.forward`` runs ``fc_out`` and the ``+ initial`` update of eligible calls
+    on the fused kernels (default) or always on the torch ops (the A/B switch of tools/bench_head.py).
+    Process-wide; returns the previous setting."""
+    global _FUSED_HEAD
+    previous, _FUSED_HEAD = _FUSED_HEAD, bool(on)
+    return previous
+
+
+class _DeformOut(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, means, quats, max_blocks, save):
+        L = _C.head_library()
+        x, w, b = x.detach().contiguous(), weight.detach().contiguous(), bias.detach().contiguous()
+        im, iq = means.detach().contiguous(), quats.detach().contiguous()
+        P, H, dev = x.shape[0], x.shape[1], x.device
+        out = torch.empty((P, 7), dtype=torch.float32, device=dev)
+        with _C._device_guard(dev):
+            _C._check(L.gsr_deform_out_forward(P, H, x.data_ptr(), w.data_ptr(), b.data_ptr(), im.data_ptr(),
+                                               iq.data_ptr(), out.data_ptr(), _C._stream_ptr(dev)))
+        ctx.saved = save
+        if save:
+            ctx.save_for_backward(x, w)
+            ctx.max_blocks = max_blocks
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        # the initial values are added as they are: their gradient is the upstream gradient's columns
+        gm = g[:, :3] if need[3] else None
+        gq = g[:, 3:] if need[4] else None
+        if not ctx.saved or not any(need[:3]):
+            return None, None, None, gm, gq, None, None
+        L = _C.head_library()
+        x, w = ctx.saved_tensors
+        P, H, dev = x.shape[0], x.shape[1], x.device
+        g = g.contiguous().float()
+        dx = torch.empty_like(x) if need[0] else None
+        dw = torch.empty_like(w) if need[1] else None
+        db = torch.empty((7,), dtype=torch.float32, device=dev) if need[2] else None
+        sums = dw is not None or db is not None
+        ws = torch.empty(max(L.gsr_deform_out_workspace_bytes(P, H, ctx.max_blocks), 1) if sums else 1,
+                         dtype=torch.uint8, device=dev)
+        with _C._device_guard(dev):
+            _C._check(L.gsr_deform_out_backward(P, H, x.data_ptr(), w.data_ptr(), g.data_ptr(), ws.data_ptr(),
+                                                ctx.max_blocks, *[t.data_ptr() if t is not None else None
+                                                                  for t in (dx, dw, db)], _C._stream_ptr(dev)))
+        return dx, dw, db, gm, gq, None, None
+
+
+def deform_output_layer(x, weight, bias, initial_params, max_blocks=0):
+    """``fc_out`` of the deformation network and the update that follows it (train.py:106-108) on the kernels
+    of csrc/gsr_head.hip: (P, 7) = ``(x @ weight.T + bias) + [initial means | initial quaternions]`` for ``x``
+    (P, H <= 512) float32 on the GPU, ``weight`` (7, H) and ``bias`` (7) as in ``nn.Linear(H, 7)``; the (P, 7)
+    concatenation is never built.  Gradients flow to ``x``, ``weight`` and ``bias``, and to the initial means
+    and quaternions when they require one (the upstream gradient's columns, as from ``out + torch.cat(...)``);
+    the graph keeps ``x`` and ``weight``.  ``max_blocks``: upper bound on the backward's persistent workgroups
+    (0: automatic)."""
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"deform_output_layer: x {tuple(x.shape)} {x.dtype}, expected float32 (P, H)")
+    P, H = x.shape
+    if not 1 <= H <= MAX_HIDDEN:
+        raise ValueError(f"deform_output_layer: hidden dimension {H} outside [1, {MAX_HIDDEN}]")
+    if tuple(weight.shape) != (7, H) or weight.dtype != torch.float32:
+        raise ValueError(f"deform_output_layer: weight {tuple(weight.shape)} {weight.dtype}, expected float32 (7, {H})")
+    if tuple(bias.shape) != (7,) or bias.dtype != torch.float32:
+        raise ValueError(f"deform_output_layer: bias {tuple(bias.shape)} {bias.dtype}, expected float32 (7,)")
+    means, quats = initial_params["means"], initial_params["rotation_quaternions"]
+    if tuple(means.shape) != (P, 3) or tuple(quats.shape) != (P, 4):
+        raise ValueError(f"deform_output_layer: means {tuple(means.shape)} / rotation_quaternions "
+                         f"{tuple(quats.shape)}, expected ({P}, 3) / ({P}, 4)")
+    for t in (means, quats):
+        if t.dtype != torch.float32:
+            raise ValueError(f"deform_output_layer: expected float32 parameters, got {t.dtype}")
+    if max_blocks < 0:
+        raise ValueError("deform_output_layer: max_blocks must be >= 0")
+    _need_gpu("x, weight, bias and params", x, weight, bias, means, quats)
+    save = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or bias.requires_grad)
+    return _DeformOut.apply(x, weight, bias, means, quats, int(max_blocks), save)
+
+
 class DeformationNetwork(nn.Module):
     """train.py:80-110 with the reference's parameter names (``fc_in``, ``residual_blocks.N.*``,
     ``fc_out``), so its checkpoints load.  ``forward`` takes the parameter dicts instead of their
-    encodings: the input layer encodes on the fly."""
+    encodings: the input layer encodes on the fly.  ``fc_out`` and the ``+ initial`` update run
+    ``deform_output_layer`` on a contiguous float32 GPU (P, H) activation with float32 GPU parameters, in
+    training and eval mode alike (unless ``set_fused_output_head(False)``); every other call the torch ops."""
 
     def __init__(self, hidden_dimension, residual_block_count):
         super().__init__()
@@ -300,10 +392,19 @@ class DeformationNetwork(nn.Module):
         self.residual_blocks = nn.Sequential(*(ResidualBlock(hidden_dimension) for _ in range(residual_block_count)))
         self.fc_out = nn.Linear(hidden_dimension, 7)
 
+    def _fused_head(self, x):
+        if not (_FUSED_HEAD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()):
+            return False
+        w, b = self.fc_out.weight, self.fc_out.bias
+        return (b is not None and tuple(w.shape) == (7, x.shape[1]) and x.shape[1] <= MAX_HIDDEN
+                and all(t.is_cuda and t.dtype == torch.float32 for t in (w, b)))
+
     def forward(self, initial_params, previous_params, timestep, timestep_count):
         out = deform_input_layer(self.fc_in.weight, self.fc_in.bias, initial_params, previous_params,
                                  timestep / timestep_count)
         out = self.residual_blocks(out)
+        if self._fused_head(out):
+            return deform_output_layer(out, self.fc_out.weight, self.fc_out.bias, initial_params)
         out = self.fc_out(out)
         return out + torch.cat((initial_params["means"], initial_params["rotation_quaternions"]), dim=1)
 

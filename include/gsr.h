@@ -467,6 +467,29 @@ int gsr_resblock_backward(int P, int H, const float *x, const float *y1, const f
                           float *dL_dbn1_weight, float *dL_dbn1_bias, float *dL_dfc2_weight, float *dL_dbn2_weight,
                           float *dL_dbn2_bias, void *stream);
 
+/* ---- Deformation network output head (additive to ABI 21) ----------------------------------------
+ * fc_out of train.py's DeformationNetwork and the "+ initial" update that follows it (train.py:106-108) on
+ * x (P, H) fp32 row-major, 0 <= P, 1 <= H <= 512:
+ *     out[p, j] = (sum_h x[p, h] weight[j, h] + bias[j]) + initial7[p, j]
+ * weight (7, H) and bias (7) as in nn.Linear(H, 7); initial7 = [initial_means (P, 3) |
+ * initial_rotation_quaternions (P, 4, raw)], read from the two arrays: the (P, 7) concatenation is never
+ * written.  The linear result is rounded first, then the initial value is added, both in fp32.  The summation
+ * order over h is fixed: two runs are bitwise equal. */
+int gsr_deform_out_forward(int P, int H, const float *x, const float *weight, const float *bias,
+                           const float *initial_means, const float *initial_rotation_quaternions, float *out,
+                           void *stream);
+/* dL_dx (P, H) = dL_dout (P, 7) weight, dL_dweight (7, H) = dL_dout^T x, dL_dbias (7) = column sums of
+ * dL_dout.  Each output may be NULL: it is then neither computed nor stored, and what is computed does not
+ * depend on which others are wanted.  x is read only for dL_dweight (it may be NULL otherwise); with dL_dx
+ * NULL nothing of size (P, H) is written.  A fixed grid of workgroups (max_blocks > 0: at most that many; 0:
+ * automatic) each writes one (7 H + 7) partial to workspace (gsr_deform_out_workspace_bytes with the same P,
+ * H, max_blocks; not needed for dL_dx alone), summed in workgroup order: no float atomics, two runs are
+ * bitwise equal.  P == 0 launches no kernel and zeroes dL_dweight and dL_dbias. */
+size_t gsr_deform_out_workspace_bytes(int P, int H, int max_blocks);
+int gsr_deform_out_backward(int P, int H, const float *x, const float *weight, const float *dL_dout,
+                            void *workspace, int max_blocks, float *dL_dx, float *dL_dweight, float *dL_dbias,
+                            void *stream);
+
 /* ---- Densification: statistics, clone / split / prune with Adam state surgery (ABI >= 4) ------
  * SURVEY.md 8(f) row 2.  Replaces update_max_2d_radii_and_visibility_mask (densify.py:154-162),
  * accumulate_mean_2d_gradients (external.py:113-124) and the body of densify_gaussians
@@ -559,7 +582,7 @@ int gsr_views_pack(int frames, int H, int W, const uint8_t *rgb, const uint8_t *
 /* Per-phase device timing with HIP events recorded on the call's stream (off by default).
  * Phases: "preprocess", "bin_count", "bin_scan", "bin_emit", "tile_sort", "render_fwd",
  * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "knn", "rigidity_fwd", "rigidity_bwd",
- * "posenc_ranges", "posenc", "deform_in_fwd", "deform_in_bwd", "resblock_fwd", "resblock_bwd".  gsr_profile_read synchronises on the recorded events. */
+ * "posenc_ranges", "posenc", "deform_in_fwd", "deform_in_bwd", "resblock_fwd", "resblock_bwd", "deform_out_fwd", "deform_out_bwd".  gsr_profile_read synchronises on the recorded events. */
 int gsr_profile_enable(int on);
 /* Restrict event recording to a comma-separated list of phases (NULL or "" = every phase), so a
  * timed region can carry the events of one kernel only.  Host-side timers are unaffected. */
