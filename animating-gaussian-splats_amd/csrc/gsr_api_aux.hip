@@ -67,11 +67,15 @@ int check_rigid(int P, int F, int k) {
     return GSR_OK;
 }
 
-constexpr int kDeformMaxH = 512;
-int check_deform(int P, int H) {
-    if (P < 0) return fail(GSR_ERR_ARG, "deform_in: P must be >= 0");
-    if (H < 1 || H > kDeformMaxH)
-        return fail(GSR_ERR_UNSUPPORTED, "deform_in: hidden dimension %d (1 to %d supported)", H, kDeformMaxH);
+// the deformation network's units: `what` is deform_in, resblock or deform_out
+int check_blocks(const char *what, int max_blocks) {
+    if (max_blocks < 0) return fail(GSR_ERR_ARG, "%s: max_blocks must be >= 0 (0: automatic)", what);
+    return GSR_OK;
+}
+
+int check_layer(const char *what, int P, int H, int max_h) {
+    if (P < 0) return fail(GSR_ERR_ARG, "%s: P must be >= 0", what);
+    if (H < 1 || H > max_h) return fail(GSR_ERR_UNSUPPORTED, "%s: hidden dimension %d (1 to %d supported)", what, H, max_h);
     return GSR_OK;
 }
 
@@ -79,15 +83,7 @@ int check_resblock(int P, int H, int max_blocks) {
     if (P < 2) return fail(GSR_ERR_ARG, "resblock: batch statistics need P >= 2 rows (got %d)", P);
     if (H < 1 || H > kResblockMaxH)
         return fail(GSR_ERR_ARG, "resblock: hidden dimension %d (1 to %d supported)", H, kResblockMaxH);
-    if (max_blocks < 0) return fail(GSR_ERR_ARG, "resblock: max_blocks must be >= 0 (0: automatic)");
-    return GSR_OK;
-}
-
-int check_head(int P, int H) {
-    if (P < 0) return fail(GSR_ERR_ARG, "deform_out: P must be >= 0");
-    if (H < 1 || H > kHeadMaxH)
-        return fail(GSR_ERR_UNSUPPORTED, "deform_out: hidden dimension %d (1 to %d supported)", H, kHeadMaxH);
-    return GSR_OK;
+    return check_blocks("resblock", max_blocks);
 }
 
 int dens_args(const gsr_densify_settings *st, DensArgs &a) {
@@ -231,7 +227,7 @@ int gsr_deform_in_forward(int P, int H, const float *initial_means, const float 
                           const float *initial_ranges, const float *previous_means,
                           const float *previous_rotation_quaternions, const float *previous_ranges, float progress,
                           const float *weight, const float *bias, float *out, void *stream) {
-    int rc = check_deform(P, H);
+    int rc = check_layer("deform_in", P, H, kDeformMaxH);
     if (rc) return rc;
     if (P == 0) return GSR_OK;
     if (!initial_means || !initial_rotation_quaternions || !initial_ranges || !previous_means ||
@@ -254,9 +250,9 @@ int gsr_deform_in_backward(int P, int H, const float *initial_means, const float
                            const float *previous_rotation_quaternions, const float *previous_ranges, float progress,
                            const float *dL_dout, void *workspace, int max_blocks, float *dL_dweight,
                            float *dL_dbias, void *stream) {
-    int rc = check_deform(P, H);
+    int rc = check_layer("deform_in", P, H, kDeformMaxH);
+    if (!rc) rc = check_blocks("deform_in", max_blocks);
     if (rc) return rc;
-    if (max_blocks < 0) return fail(GSR_ERR_ARG, "deform_in: max_blocks must be >= 0 (0: automatic)");
     if (!dL_dweight && !dL_dbias) return GSR_OK;
     if (P == 0) return fail(GSR_ERR_ARG, "deform_in: no rows to sum the gradient over");
     if (!initial_means || !initial_rotation_quaternions || !initial_ranges || !previous_means ||
@@ -321,7 +317,7 @@ int gsr_resblock_backward(int P, int H, const float *x, const float *y1, const f
 int gsr_deform_out_forward(int P, int H, const float *x, const float *weight, const float *bias,
                            const float *initial_means, const float *initial_rotation_quaternions, float *out,
                            void *stream) {
-    int rc = check_head(P, H);
+    int rc = check_layer("deform_out", P, H, kHeadMaxH);
     if (rc) return rc;
     if (P == 0) return GSR_OK;
     if (!x || !weight || !bias || !initial_means || !initial_rotation_quaternions || !out)
@@ -339,9 +335,9 @@ size_t gsr_deform_out_workspace_bytes(int P, int H, int max_blocks) {
 
 int gsr_deform_out_backward(int P, int H, const float *x, const float *weight, const float *dL_dout, void *workspace,
                             int max_blocks, float *dL_dx, float *dL_dweight, float *dL_dbias, void *stream) {
-    int rc = check_head(P, H);
+    int rc = check_layer("deform_out", P, H, kHeadMaxH);
+    if (!rc) rc = check_blocks("deform_out", max_blocks);
     if (rc) return rc;
-    if (max_blocks < 0) return fail(GSR_ERR_ARG, "deform_out: max_blocks must be >= 0 (0: automatic)");
     if (!dL_dx && !dL_dweight && !dL_dbias) return GSR_OK;
     hipStream_t s = (hipStream_t)stream;
     if (P == 0) {  // empty sums: no kernel

@@ -35,6 +35,7 @@
 //                       dW[:, 184 + j] = enc(progress)_j db.
 #include "gsr_common.h"
 #include "gsr_internal.h"
+#include "gsr_mlp.h"
 
 namespace gsr {
 
@@ -57,9 +58,6 @@ constexpr int kFwdMTiles = kFwdRows / 32;                    // 32-row tiles of 
 constexpr int kFwdNGroups = kFwdThreads / 64 / kFwdMTiles;   // waves that share a row tile split the column tiles
 static_assert(kFwdMTiles * 32 == kFwdRows && kFwdNGroups * kFwdMTiles * 64 == kFwdThreads && kFwdNGroups >= 1, "forward tiling");
 constexpr int kBwdRows = 64, kBwdThreads = 512;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // argument a in [0, 46) of a pair: its input column (0-2 means, 3-6 quaternion), frequency index and the
 // feature slots of its sine and of the cosine of that sine
@@ -251,7 +249,7 @@ __global__ __launch_bounds__(kFwdThreads) void k_deform_in_fwd(DeformIn a, const
         for (int q = 0; q < 8; ++q) c = fmaf(W[(size_t)h * kInCols + kXCols + q], pe[q], c);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = row0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int row = row0 + mt * 32 + acc_row(r, lane);
             if (row < a.P) Y[(size_t)row * a.H + h] = acc[j][r] + c;
         }
     }
@@ -352,25 +350,7 @@ void split_h(int H, int &ny, int &nt) {
     nt = div_up(div_up(H, 32), ny);
 }
 
-template <int NT>
-hipError_t run_fwd(const DeformIn &a, int ny, const float *W, const float *bias, float *Y, hipStream_t s) {
-    constexpr int WS = NT * 32 + 1;
-    constexpr int second = 14 * kFwdRows > kWChunk * WS ? 14 * kFwdRows : kWChunk * WS;
-    constexpr size_t lds = sizeof(float) * (kFwdRows * kXStride + second);
-    hipError_t e = hipFuncSetAttribute((const void *)k_deform_in_fwd<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    k_deform_in_fwd<NT><<<dim3(div_up(a.P, kFwdRows), ny), kFwdThreads, lds, s>>>(a, W, bias, Y);
-    return hipGetLastError();
-}
-
-template <int MT>
-hipError_t run_bwd(const DeformIn &a, int nb, int ny, int tiles, const float *dY, float *partial, hipStream_t s) {
-    constexpr size_t lds = sizeof(float) * (kBwdRows * kXStride + 14 * kBwdRows + kBwdRows * (MT * 32 + 16));
-    hipError_t e = hipFuncSetAttribute((const void *)k_deform_in_bwd<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    k_deform_in_bwd<MT><<<dim3(nb, ny), kBwdThreads, lds, s>>>(a, tiles, dY, partial);
-    return hipGetLastError();
-}
+int deform_in_blocks(int P, int max_blocks) { return persistent_blocks(P, kBwdRows, max_blocks, kDeformAutoBlocks); }
 }  // namespace
 
 hipError_t launch_posenc_ranges(int P, const float *means, const float *quats, float *partial, float *ranges,
@@ -393,18 +373,12 @@ hipError_t launch_deform_in_fwd(int P, int H, const float *im, const float *iq, 
     const DeformIn a = deform_in(P, H, im, iq, ir, pm, pq, pr, progress);
     int ny, nt;
     split_h(H, ny, nt);
-    switch (nt) {
-    case 1: return run_fwd<1>(a, ny, W, bias, Y, s);
-    case 2: return run_fwd<2>(a, ny, W, bias, Y, s);
-    case 3: return run_fwd<3>(a, ny, W, bias, Y, s);
-    default: return run_fwd<4>(a, ny, W, bias, Y, s);
-    }
-}
-
-int deform_in_blocks(int P, int max_blocks) {
-    const int tiles = div_up(P, kBwdRows);
-    const int cap = max_blocks > 0 ? max_blocks : kDeformAutoBlocks;
-    return tiles < cap ? tiles : cap;
+    return dispatch_tiles(nt, [&](auto n) {
+        constexpr int NT = decltype(n)::value, WS = NT * 32 + 1;
+        constexpr int second = 14 * kFwdRows > kWChunk * WS ? 14 * kFwdRows : kWChunk * WS;
+        return launch_lds(k_deform_in_fwd<NT>, dim3(div_up(P, kFwdRows), ny), kFwdThreads,
+                          sizeof(float) * (kFwdRows * kXStride + second), s, a, W, bias, Y);
+    });
 }
 
 size_t deform_in_partial_floats(int P, int H, int max_blocks) {
@@ -418,13 +392,12 @@ hipError_t launch_deform_in_bwd(int P, int H, const float *im, const float *iq, 
     const int nb = deform_in_blocks(P, max_blocks), tiles = div_up(P, kBwdRows);
     int ny, mt;
     split_h(H, ny, mt);
-    hipError_t e;
-    switch (mt) {
-    case 1: e = run_bwd<1>(a, nb, ny, tiles, dY, partial, s); break;
-    case 2: e = run_bwd<2>(a, nb, ny, tiles, dY, partial, s); break;
-    case 3: e = run_bwd<3>(a, nb, ny, tiles, dY, partial, s); break;
-    default: e = run_bwd<4>(a, nb, ny, tiles, dY, partial, s); break;
-    }
+    hipError_t e = dispatch_tiles(mt, [&](auto m) {
+        constexpr int MT = decltype(m)::value;
+        return launch_lds(k_deform_in_bwd<MT>, dim3(nb, ny), kBwdThreads,
+                          sizeof(float) * (kBwdRows * kXStride + 14 * kBwdRows + kBwdRows * (MT * 32 + 16)), s, a, tiles,
+                          dY, partial);
+    });
     if (e != hipSuccess) return e;
     k_deform_in_reduce<<<div_up(H * kInCols, 256), 256, 0, s>>>(H, nb, partial, progress, dW, db);
     return hipGetLastError();

@@ -30,6 +30,7 @@
 //                       of loads that takes longer than k_head_bwd itself.
 #include "gsr_common.h"
 #include "gsr_internal.h"
+#include "gsr_mlp.h"
 
 namespace gsr {
 
@@ -39,8 +40,6 @@ constexpr int kSlots = kThreads / 16;       // the forward's row slots
 constexpr int kPasses = kRows / kSlots;     // rows of a tile per slot
 constexpr int kFwdTiles = 4;                // consecutive row tiles of a forward workgroup
 constexpr int kTileOut = kRows * 7;         // upstream gradients of a row tile
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // sum over the 16 lanes of a DPP row, the same tree in every lane
 __device__ inline float row16_sum(float v) {
@@ -292,6 +291,8 @@ void run_fwd(int nb, int P, int H, int tiles, const float *x, const float *W, co
     else k_head_fwd<VEC, false><<<nb, kThreads, sizeof(float) * 7 * div_up(H, kChunk) * kChunk, s>>>(P, H, tiles, x, W, bias,
                                                                                                    im, iq, out);
 }
+
+int head_blocks(int P, int max_blocks) { return persistent_blocks(P, kRows, max_blocks, kHeadAutoBlocks); }
 }  // namespace
 
 hipError_t launch_head_fwd(int P, int H, const float *x, const float *W, const float *bias, const float *im,
@@ -300,12 +301,6 @@ hipError_t launch_head_fwd(int P, int H, const float *x, const float *W, const f
     if (H % 4 == 0 && aligned16(x)) run_fwd<true>(nb, P, H, tiles, x, W, bias, im, iq, out, s);
     else run_fwd<false>(nb, P, H, tiles, x, W, bias, im, iq, out, s);
     return hipGetLastError();
-}
-
-int head_blocks(int P, int max_blocks) {
-    const int tiles = div_up(P, kRows);
-    const int cap = max_blocks > 0 ? max_blocks : kHeadAutoBlocks;
-    return tiles < cap ? tiles : cap;
 }
 
 size_t head_partial_floats(int P, int H, int max_blocks) { return (size_t)head_blocks(P, max_blocks) * (7 * (size_t)H + 7); }

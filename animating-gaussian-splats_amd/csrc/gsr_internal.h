@@ -139,6 +139,7 @@ hipError_t launch_rigid_bwd(int P, int F, int k, const int *row_to_fg, const int
 
 // deformation network input layer (gsr_deform.hip): i* initial, p* previous (means, quats, ranges)
 constexpr int kDeformAutoBlocks = 256;  // persistent backward workgroups when the caller sets no bound (one per CU)
+constexpr int kDeformMaxH = 512;
 constexpr int kPosencRangeBlocks = 256;  // = GSR_POSENC_RANGE_BLOCKS: workgroups (partials) of the range reduction
 hipError_t launch_posenc_ranges(int P, const float *means, const float *quats, float *partial, float *ranges,
                                 hipStream_t s);
@@ -146,7 +147,6 @@ hipError_t launch_posenc(int P, const float *means, const float *quats, const fl
 hipError_t launch_deform_in_fwd(int P, int H, const float *im, const float *iq, const float *ir, const float *pm,
                                 const float *pq, const float *pr, float progress, const float *W, const float *bias,
                                 float *Y, hipStream_t s);
-int deform_in_blocks(int P, int max_blocks);
 size_t deform_in_partial_floats(int P, int H, int max_blocks);
 hipError_t launch_deform_in_bwd(int P, int H, const float *im, const float *iq, const float *ir, const float *pm,
                                 const float *pq, const float *pr, float progress, const float *dY, float *partial,
@@ -176,7 +176,6 @@ constexpr int kHeadAutoBlocks = 1024;  // persistent backward workgroups when th
 constexpr int kHeadMaxH = 512;
 hipError_t launch_head_fwd(int P, int H, const float *x, const float *W, const float *bias, const float *im,
                            const float *iq, float *out, hipStream_t s);
-int head_blocks(int P, int max_blocks);
 size_t head_partial_floats(int P, int H, int max_blocks);
 hipError_t launch_head_bwd(int P, int H, const float *x, const float *W, const float *g, float *partial, int max_blocks,
                            float *dx, float *dW, float *db, hipStream_t s);

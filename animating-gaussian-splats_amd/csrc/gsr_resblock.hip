@@ -28,14 +28,13 @@
 //   k_res_reduce_w           sums the dW partials in workgroup order.
 #include "gsr_common.h"
 #include "gsr_internal.h"
+#include "gsr_mlp.h"
 
 namespace gsr {
 
 namespace {
 constexpr int kRows = 64, kThreads = 512, kEwThreads = 256;
 constexpr int kOutBlocks = 1024;  // workgroups of k_res_bwd_out when the caller sets no bound
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct BnCols { const float *mean, *invstd, *gamma, *beta; };
 
@@ -57,8 +56,29 @@ __device__ inline void chan(double &n, double &mean, double &m2, double nb, doub
     n = tot;
 }
 
-// row of accumulator register r of a 32 x 32 MFMA result (the column is lane & 31)
-__device__ inline int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+// column i of (mean, invstd, gamma, beta) into cols[0 .. 4 HP), HP floats each, zeros past H
+template <int HP>
+__device__ inline void stage_bn(float *cols, const BnCols &bn, int i, int H) {
+    const bool in = i < H;
+    cols[i] = in ? bn.mean[i] : 0.f;
+    cols[HP + i] = in ? bn.invstd[i] : 0.f;
+    cols[2 * HP + i] = in ? bn.gamma[i] : 0.f;
+    cols[3 * HP + i] = in ? bn.beta[i] : 0.f;
+}
+
+// gelu(bn(v)) of column c from the staged columns
+template <int HP>
+__device__ inline float bn_gelu(float v, const float *cols, int c) {
+    return gelu_f(((v - cols[c]) * cols[HP + c]) * cols[2 * HP + c] + cols[3 * HP + c]);
+}
+
+// prefetch slot q of thread t: row r and column c of the kRows x HP tile
+template <int HP>
+__device__ inline void slot_rc(int t, int q, int &r, int &c) {
+    const int i = t + q * kThreads;
+    r = i / HP;
+    c = i - r * HP;
+}
 }  // namespace
 
 template <int NT, bool PRO>
@@ -79,13 +99,7 @@ __global__ __launch_bounds__(kThreads) void k_res_gemm(int P, int H, int tiles, 
         Ws[k * WS + j] = j < H && k < H ? W[(size_t)j * H + k] : 0.f;
     }
     if (PRO)
-        for (int i = t; i < HP; i += kThreads) {
-            const bool in = i < H;
-            cols[i] = in ? bn.mean[i] : 0.f;
-            cols[HP + i] = in ? bn.invstd[i] : 0.f;
-            cols[2 * HP + i] = in ? bn.gamma[i] : 0.f;
-            cols[3 * HP + i] = in ? bn.beta[i] : 0.f;
-        }
+        for (int i = t; i < HP; i += kThreads) stage_bn<HP>(cols, bn, i, H);
     double rn = 0.0, rmean = 0.0, rm2 = 0.0;  // thread t < H: column t over this workgroup's tiles
     const float *xa = Xs + (mt * 32 + (lane & 31)) * XS + (lane >> 5);
     const float *wb = Ws + (lane >> 5) * WS + nt * 32 + (lane & 31);
@@ -96,7 +110,8 @@ __global__ __launch_bounds__(kThreads) void k_res_gemm(int P, int H, int tiles, 
     auto fetch = [&](int tile) {
 #pragma unroll
         for (int q = 0; q < NL; ++q) {
-            const int i = t + q * kThreads, r = i / HP, c = i - r * HP;
+            int r, c;
+            slot_rc<HP>(t, q, r, c);
             const int row = tile * kRows + r;
             pre[q] = row < P && c < H ? X[(size_t)row * H + c] : 0.f;
         }
@@ -108,10 +123,10 @@ __global__ __launch_bounds__(kThreads) void k_res_gemm(int P, int H, int tiles, 
         lds_barrier();  // W and the column constants are visible / the previous tile has been consumed
 #pragma unroll
         for (int q = 0; q < NL; ++q) {
-            const int i = t + q * kThreads, r = i / HP, c = i - r * HP;
+            int r, c;
+            slot_rc<HP>(t, q, r, c);
             float v = pre[q];
-            if (PRO && row0 + r < P && c < H)
-                v = gelu_f(((v - cols[c]) * cols[HP + c]) * cols[2 * HP + c] + cols[3 * HP + c]);
+            if (PRO && row0 + r < P && c < H) v = bn_gelu<HP>(v, cols, c);
             Xs[r * XS + c] = v;
         }
         lds_barrier();
@@ -312,12 +327,7 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_gemm(int P, int H, int til
         colsG[2 * HP + i] = in ? bnG.gamma[i] * is : 0.f;
         colsG[3 * HP + i] = in ? sums[i] / (float)P : 0.f;
         colsG[4 * HP + i] = in ? sums[H + i] / (float)P : 0.f;
-        if (STAGE == 2) {
-            colsA[i] = in ? bnA.mean[i] : 0.f;
-            colsA[HP + i] = in ? bnA.invstd[i] : 0.f;
-            colsA[2 * HP + i] = in ? bnA.gamma[i] : 0.f;
-            colsA[3 * HP + i] = in ? bnA.beta[i] : 0.f;
-        }
+        if (STAGE == 2) stage_bn<HP>(colsA, bnA, i, H);
     }
     f32x16 dw[NQ];
 #pragma unroll
@@ -332,7 +342,8 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_gemm(int P, int H, int til
     auto fetch = [&](int tile) {
 #pragma unroll
         for (int q = 0; q < NL; ++q) {
-            const int i = t + q * kThreads, r = i / HP, c = i - r * HP;
+            int r, c;
+            slot_rc<HP>(t, q, r, c);
             const int row = tile * kRows + r;
             const bool in = row < P && c < H;
             const size_t at = (size_t)row * H + c;
@@ -348,14 +359,14 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_gemm(int P, int H, int til
         lds_barrier();  // W and the column constants are visible / the previous tile has been consumed
 #pragma unroll
         for (int q = 0; q < NL; ++q) {
-            const int i = t + q * kThreads, r = i / HP, c = i - r * HP;
+            int r, c;
+            slot_rc<HP>(t, q, r, c);
             float gy = 0.f, a = 0.f;
             if (row0 + r < P && c < H) {
                 const float xh = (py[q] - colsG[c]) * colsG[HP + c];
                 gy = colsG[2 * HP + c] * ((pg[q] - colsG[3 * HP + c]) - xh * colsG[4 * HP + c]);
                 a = pa[q];
-                if (STAGE == 2 && want_w)
-                    a = gelu_f(((a - colsA[c]) * colsA[HP + c]) * colsA[2 * HP + c] + colsA[3 * HP + c]);
+                if (STAGE == 2 && want_w) a = bn_gelu<HP>(a, colsA, c);
             }
             Gs[r * XS + c] = gy;
             As[r * XS + c] = a;
@@ -454,66 +465,32 @@ size_t bwd_lds(int nt) {
     return sizeof(float) * ((size_t)2 * tile + (tile & 1) + 9 * HP + (size_t)HP * (HP + 1));
 }
 
-template <int NT, bool PRO>
-hipError_t run_gemm(int nb, int P, int H, const float *X, const float *W, const BnCols &bn, float *Y, double *partial,
-                    hipStream_t s) {
-    const size_t lds = fwd_lds(NT);
-    hipError_t e = hipFuncSetAttribute((const void *)k_res_gemm<NT, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    k_res_gemm<NT, PRO><<<nb, kThreads, lds, s>>>(P, H, div_up(P, kRows), X, W, bn, Y, partial);
-    return hipGetLastError();
-}
-
 template <bool PRO>
 hipError_t gemm(int nb, int P, int H, const float *X, const float *W, const BnCols &bn, float *Y, double *partial,
                 hipStream_t s) {
-    switch (res_nt(H)) {
-    case 1: return run_gemm<1, PRO>(nb, P, H, X, W, bn, Y, partial, s);
-    case 2: return run_gemm<2, PRO>(nb, P, H, X, W, bn, Y, partial, s);
-    case 3: return run_gemm<3, PRO>(nb, P, H, X, W, bn, Y, partial, s);
-    default: return run_gemm<4, PRO>(nb, P, H, X, W, bn, Y, partial, s);
-    }
-}
-
-template <int NT, int STAGE>
-hipError_t run_bwd_gemm(int nb, int P, int H, const float *g_in, const float *yn, const BnCols &bnG, const float *sums,
-                        const float *a_in, const BnCols &bnA, const float *W, const float *g_s, float *g_out,
-                        float *partialW, double *partialS, hipStream_t s) {
-    const size_t lds = bwd_lds(NT);
-    hipError_t e = hipFuncSetAttribute((const void *)k_res_bwd_gemm<NT, STAGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    k_res_bwd_gemm<NT, STAGE><<<nb, kThreads, lds, s>>>(P, H, div_up(P, kRows), g_in, yn, bnG, sums, a_in, bnA, W, g_s,
-                                                        g_out, partialW, partialS);
-    return hipGetLastError();
+    return dispatch_tiles(res_nt(H), [&](auto n) {
+        constexpr int NT = decltype(n)::value;
+        return launch_lds(k_res_gemm<NT, PRO>, nb, kThreads, fwd_lds(NT), s, P, H, div_up(P, kRows), X, W, bn, Y, partial);
+    });
 }
 
 template <int STAGE>
 hipError_t bwd_gemm(int nb, int P, int H, const float *g_in, const float *yn, const BnCols &bnG, const float *sums,
                     const float *a_in, const BnCols &bnA, const float *W, const float *g_s, float *g_out, float *partialW,
                     double *partialS, hipStream_t s) {
-    switch (res_nt(H)) {
-    case 1: return run_bwd_gemm<1, STAGE>(nb, P, H, g_in, yn, bnG, sums, a_in, bnA, W, g_s, g_out, partialW, partialS, s);
-    case 2: return run_bwd_gemm<2, STAGE>(nb, P, H, g_in, yn, bnG, sums, a_in, bnA, W, g_s, g_out, partialW, partialS, s);
-    case 3: return run_bwd_gemm<3, STAGE>(nb, P, H, g_in, yn, bnG, sums, a_in, bnA, W, g_s, g_out, partialW, partialS, s);
-    default: return run_bwd_gemm<4, STAGE>(nb, P, H, g_in, yn, bnG, sums, a_in, bnA, W, g_s, g_out, partialW, partialS, s);
-    }
+    return dispatch_tiles(res_nt(H), [&](auto n) {
+        constexpr int NT = decltype(n)::value;
+        return launch_lds(k_res_bwd_gemm<NT, STAGE>, nb, kThreads, bwd_lds(NT), s, P, H, div_up(P, kRows), g_in, yn, bnG,
+                          sums, a_in, bnA, W, g_s, g_out, partialW, partialS);
+    });
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-}  // namespace
-
+// H <= 64: two workgroups fit a CU's LDS
 int resblock_blocks(int P, int H, int max_blocks) {
-    const int tiles = div_up(P, kRows);
-    // H <= 64: two workgroups fit a CU's LDS
-    const int cap = max_blocks > 0 ? max_blocks : kResblockAutoBlocks * (H <= 64 ? 2 : 1);
-    return tiles < cap ? tiles : cap;
+    return persistent_blocks(P, kRows, max_blocks, kResblockAutoBlocks * (H <= 64 ? 2 : 1));
 }
-
-int resblock_out_blocks(int P, int max_blocks) {
-    const int tiles = div_up(P, kRows);
-    const int cap = max_blocks > 0 ? max_blocks : kOutBlocks;
-    return tiles < cap ? tiles : cap;
-}
+int resblock_out_blocks(int P, int max_blocks) { return persistent_blocks(P, kRows, max_blocks, kOutBlocks); }
+}  // namespace
 
 ResblockWorkspace::ResblockWorkspace(int P, int H, int max_blocks, bool backward) {
     const size_t nb = (size_t)resblock_blocks(P, H, max_blocks), no = (size_t)resblock_out_blocks(P, max_blocks);

@@ -192,43 +192,14 @@ def load_library():
     L.gsr_rigidity_forward.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, vp]
     L.gsr_rigidity_backward.restype = i
     L.gsr_rigidity_backward.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
-    global _DEFORM_MISSING
-    try:  # additive to ABI 21: a library built before them still serves everything else
-        L.gsr_posenc_ranges.restype = i
-        L.gsr_posenc_ranges.argtypes = [i, vp, vp, vp, vp, vp]
-        L.gsr_posenc_forward.restype = i
-        L.gsr_posenc_forward.argtypes = [i, vp, vp, vp, vp, vp]
-        L.gsr_deform_in_forward.restype = i
-        L.gsr_deform_in_forward.argtypes = [i, i, vp, vp, vp, vp, vp, vp, f, vp, vp, vp, vp]
-        L.gsr_deform_in_workspace_bytes.restype = ctypes.c_size_t
-        L.gsr_deform_in_workspace_bytes.argtypes = [i, i, i]
-        L.gsr_deform_in_backward.restype = i
-        L.gsr_deform_in_backward.argtypes = [i, i, vp, vp, vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp]
-        _DEFORM_MISSING = None
-    except AttributeError as err:
-        _DEFORM_MISSING = str(err)
-    global _RESBLOCK_MISSING
-    try:  # likewise additive to ABI 21
-        L.gsr_resblock_workspace_bytes.restype = ctypes.c_size_t
-        L.gsr_resblock_workspace_bytes.argtypes = [i, i, i, i]
-        L.gsr_resblock_forward.restype = i
-        L.gsr_resblock_forward.argtypes = [i, i] + [vp] * 7 + [f] * 4 + [vp] * 5 + [i] + [vp] * 5
-        L.gsr_resblock_backward.restype = i
-        L.gsr_resblock_backward.argtypes = [i, i] + [vp] * 12 + [i] + [vp] * 8
-        _RESBLOCK_MISSING = None
-    except AttributeError as err:
-        _RESBLOCK_MISSING = str(err)
-    global _HEAD_MISSING
-    try:  # likewise additive to ABI 21
-        L.gsr_deform_out_forward.restype = i
-        L.gsr_deform_out_forward.argtypes = [i, i] + [vp] * 7
-        L.gsr_deform_out_workspace_bytes.restype = ctypes.c_size_t
-        L.gsr_deform_out_workspace_bytes.argtypes = [i, i, i]
-        L.gsr_deform_out_backward.restype = i
-        L.gsr_deform_out_backward.argtypes = [i, i, vp, vp, vp, vp, i, vp, vp, vp, vp]
-        _HEAD_MISSING = None
-    except AttributeError as err:
-        _HEAD_MISSING = str(err)
+    _MISSING.clear()
+    for feature, (_, symbols) in _OPTIONAL.items():
+        try:
+            for name, (restype, argtypes) in symbols.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
+        except AttributeError as err:
+            _MISSING[feature] = str(err)
     if L.gsr_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libgsr.so ABI {L.gsr_abi_version()} != binding ABI {ABI_VERSION}: rebuild it")
     global _PREALLOC_FN
@@ -240,41 +211,40 @@ def load_library():
 ABI_VERSION = 21  # GSR_ABI_VERSION of include/gsr.h this binding's structs follow
 ACT_SIGMOID_OPACITY, ACT_EXP_SCALES, ACT_NORMALIZE_ROTATIONS = 1, 2, 4  # enum gsr_activation
 ACT_ALL = ACT_SIGMOID_OPACITY | ACT_EXP_SCALES | ACT_NORMALIZE_ROTATIONS
-_DEFORM_MISSING = None  # why the deformation input layer's entry points could not be bound (a stale libgsr.so)
 
 
-def deform_library():
-    """The library, for the deformation input layer (splat_deform): raises when ``libgsr.so`` predates
-    its entry points, on first use of the feature only."""
+def _optional():
+    vp, i, f, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+    return {
+        "deform": ("the deformation input layer", {
+            "gsr_posenc_ranges": (i, [i, vp, vp, vp, vp, vp]),
+            "gsr_posenc_forward": (i, [i, vp, vp, vp, vp, vp]),
+            "gsr_deform_in_forward": (i, [i, i, vp, vp, vp, vp, vp, vp, f, vp, vp, vp, vp]),
+            "gsr_deform_in_workspace_bytes": (sz, [i, i, i]),
+            "gsr_deform_in_backward": (i, [i, i, vp, vp, vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp])}),
+        "resblock": ("the fused residual blocks", {
+            "gsr_resblock_workspace_bytes": (sz, [i, i, i, i]),
+            "gsr_resblock_forward": (i, [i, i] + [vp] * 7 + [f] * 4 + [vp] * 5 + [i] + [vp] * 5),
+            "gsr_resblock_backward": (i, [i, i] + [vp] * 12 + [i] + [vp] * 8)}),
+        "head": ("the fused output head", {
+            "gsr_deform_out_forward": (i, [i, i] + [vp] * 7),
+            "gsr_deform_out_workspace_bytes": (sz, [i, i, i]),
+            "gsr_deform_out_backward": (i, [i, i, vp, vp, vp, vp, i, vp, vp, vp, vp])}),
+    }
+
+
+# Entry points additive to ABI 21, so that a library built before them still serves everything else:
+# feature -> (its name in the error message, {symbol: (restype, argtypes)}).
+_OPTIONAL = _optional()
+_MISSING = {}  # feature -> why its entry points could not be bound (a stale libgsr.so)
+
+
+def feature_library(name):
+    """The library, for the optional feature ``name`` of splat_deform ("deform", "resblock" or "head"): raises
+    when ``libgsr.so`` predates its entry points, on first use of the feature only."""
     L = load_library()
-    if _DEFORM_MISSING is not None:
-        raise RuntimeError(f"libgsr.so at {LIB_PATH} lacks the deformation input layer ({_DEFORM_MISSING}): "
-                           "rebuild it with `make -C animating-gaussian-splats_amd/csrc`")
-    return L
-
-
-_RESBLOCK_MISSING = None  # likewise for the fused residual blocks' entry points
-
-
-def resblock_library():
-    """The library, for the fused residual blocks (splat_deform.residual_block): raises when
-    ``libgsr.so`` predates their entry points, on first use of the feature only."""
-    L = load_library()
-    if _RESBLOCK_MISSING is not None:
-        raise RuntimeError(f"libgsr.so at {LIB_PATH} lacks the fused residual blocks ({_RESBLOCK_MISSING}): "
-                           "rebuild it with `make -C animating-gaussian-splats_amd/csrc`")
-    return L
-
-
-_HEAD_MISSING = None  # likewise for the fused output head's entry points
-
-
-def head_library():
-    """The library, for the fused output head (splat_deform.deform_output_layer): raises when
-    ``libgsr.so`` predates its entry points, on first use of the feature only."""
-    L = load_library()
-    if _HEAD_MISSING is not None:
-        raise RuntimeError(f"libgsr.so at {LIB_PATH} lacks the fused output head ({_HEAD_MISSING}): "
+    if name in _MISSING:
+        raise RuntimeError(f"libgsr.so at {LIB_PATH} lacks {_OPTIONAL[name][0]} ({_MISSING[name]}): "
                            "rebuild it with `make -C animating-gaussian-splats_amd/csrc`")
     return L
 

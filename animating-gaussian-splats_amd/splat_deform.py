@@ -42,17 +42,41 @@ INPUT_WIDTH = 192    # two encodings + the 8 progress columns
 RANGE_BLOCKS = 256   # GSR_POSENC_RANGE_BLOCKS of include/gsr.h
 
 
-def _means_and_rotations(params, what):
-    """The (P, 3) means and (P, 4) raw quaternions of ``params``, detached, fp32, contiguous."""
+def _param_tensors(params, what, P=None):
+    """The (P, 3) means and (P, 4) raw quaternions of ``params`` as they are (attached), checked to be fp32 and
+    to have ``P`` rows (None: as many as the means have)."""
     means, quats = params["means"], params["rotation_quaternions"]
-    P = means.shape[0] if means.dim() else -1
+    rows = "P" if P is None else P
+    if P is None:
+        P = means.shape[0] if means.dim() else -1
     if tuple(means.shape) != (P, 3) or tuple(quats.shape) != (P, 4):
         raise ValueError(f"{what}: means {tuple(means.shape)} / rotation_quaternions {tuple(quats.shape)}, "
-                         f"expected (P, 3) / (P, 4)")
+                         f"expected ({rows}, 3) / ({rows}, 4)")
     for t in (means, quats):
         if t.dtype != torch.float32:
             raise ValueError(f"{what}: expected float32 parameters, got {t.dtype}")
+    return means, quats
+
+
+def _means_and_rotations(params, what):
+    """The (P, 3) means and (P, 4) raw quaternions of ``params``, detached, fp32, contiguous."""
+    means, quats = _param_tensors(params, what)
     return means.detach().contiguous(), quats.detach().contiguous()
+
+
+def _check_activation(x, what, max_hidden):
+    """(P, H) of ``x``, checked to be a float32 matrix with 1 <= H <= ``max_hidden``."""
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"{what}: x {tuple(x.shape)} {x.dtype}, expected float32 (P, H)")
+    P, H = x.shape
+    if not 1 <= H <= max_hidden:
+        raise ValueError(f"{what}: hidden dimension {H} outside [1, {max_hidden}]")
+    return P, H
+
+
+def _check_blocks(max_blocks, what):
+    if max_blocks < 0:
+        raise ValueError(f"{what}: max_blocks must be >= 0")
 
 
 def _need_gpu(what, *tensors):
@@ -61,17 +85,35 @@ def _need_gpu(what, *tensors):
             raise RuntimeError(f"splat_deform: {what} must be on the GPU (no CPU path)")
 
 
+def _eligible(x, *params):
+    """The tensor tests of the fused paths: a contiguous (P, H) activation, and it and ``params`` float32 on the GPU."""
+    return x.dim() == 2 and x.is_contiguous() and all(t.is_cuda and t.dtype == torch.float32 for t in (x, *params))
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _workspace(nbytes, dev):
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+
+
+def _call(dev, fn, *args):
+    """The entry point ``fn`` of libgsr on ``dev`` and its current stream (every entry point's last argument)."""
+    with _C._device_guard(dev):
+        _C._check(fn(*args, _C._stream_ptr(dev)))
+
+
 def encoding_ranges(means, quats):
     """The 14 floats the normalisation needs: per column (means xyz, quaternion wxyz) the minimum and
     the maximum of ``x - minimum`` (train.py:190-197), exact in fp32: one pass over the (P >= 1) rows."""
-    L = _C.deform_library()
+    L = _C.feature_library("deform")
     dev = means.device
     if means.shape[0] == 0:
         return torch.zeros(14, dtype=torch.float32, device=dev)
     buf = torch.empty(14 * (RANGE_BLOCKS + 1), dtype=torch.float32, device=dev)  # the ranges, then the partials
-    with _C._device_guard(dev):
-        _C._check(L.gsr_posenc_ranges(means.shape[0], means.data_ptr(), quats.data_ptr(), buf[14:].data_ptr(),
-                                      buf.data_ptr(), _C._stream_ptr(dev)))
+    _call(dev, L.gsr_posenc_ranges, means.shape[0], means.data_ptr(), quats.data_ptr(), buf[14:].data_ptr(),
+          buf.data_ptr())
     return buf[:14]
 
 
@@ -79,29 +121,25 @@ def encode_means_and_rotations(params):
     """train.py:185-204 ``normalize_and_encode_means_and_rotations``: (P, 92) float32."""
     means, quats = _means_and_rotations(params, "encode_means_and_rotations")
     _need_gpu("params", means, quats)
-    L = _C.deform_library()
+    L = _C.feature_library("deform")
     P, dev = means.shape[0], means.device
     out = torch.empty((P, ENCODING_WIDTH), dtype=torch.float32, device=dev)
     if P == 0:
         return out
     ranges = encoding_ranges(means, quats)
-    with _C._device_guard(dev):
-        _C._check(L.gsr_posenc_forward(P, means.data_ptr(), quats.data_ptr(), ranges.data_ptr(), out.data_ptr(),
-                                       _C._stream_ptr(dev)))
+    _call(dev, L.gsr_posenc_forward, P, means.data_ptr(), quats.data_ptr(), ranges.data_ptr(), out.data_ptr())
     return out
 
 
 class _DeformIn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, bias, im, iq, ir, pm, pq, pr, progress, max_blocks, save):
-        L = _C.deform_library()
+        L = _C.feature_library("deform")
         w, b = weight.detach().contiguous(), bias.detach().contiguous()
         P, H, dev = im.shape[0], w.shape[0], im.device
         out = torch.empty((P, H), dtype=torch.float32, device=dev)
-        with _C._device_guard(dev):
-            _C._check(L.gsr_deform_in_forward(P, H, im.data_ptr(), iq.data_ptr(), ir.data_ptr(), pm.data_ptr(),
-                                              pq.data_ptr(), pr.data_ptr(), progress, w.data_ptr(), b.data_ptr(),
-                                              out.data_ptr(), _C._stream_ptr(dev)))
+        _call(dev, L.gsr_deform_in_forward, P, H, im.data_ptr(), iq.data_ptr(), ir.data_ptr(), pm.data_ptr(),
+              pq.data_ptr(), pr.data_ptr(), progress, w.data_ptr(), b.data_ptr(), out.data_ptr())
         if save:
             ctx.save_for_backward(im, iq, ir, pm, pq, pr)
             ctx.progress, ctx.max_blocks, ctx.H = progress, max_blocks, H
@@ -109,7 +147,7 @@ class _DeformIn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        L = _C.deform_library()
+        L = _C.feature_library("deform")
         im, iq, ir, pm, pq, pr = ctx.saved_tensors
         P, H, dev = im.shape[0], ctx.H, im.device
         g = g.contiguous().float()
@@ -117,12 +155,10 @@ class _DeformIn(torch.autograd.Function):
         db = torch.empty((H,), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         if P == 0:
             return (dw.zero_() if dw is not None else None, db.zero_() if db is not None else None) + (None,) * 9
-        ws = torch.empty(max(L.gsr_deform_in_workspace_bytes(P, H, ctx.max_blocks), 1), dtype=torch.uint8, device=dev)
-        with _C._device_guard(dev):
-            _C._check(L.gsr_deform_in_backward(P, H, im.data_ptr(), iq.data_ptr(), ir.data_ptr(), pm.data_ptr(),
-                                               pq.data_ptr(), pr.data_ptr(), ctx.progress, g.data_ptr(), ws.data_ptr(),
-                                               ctx.max_blocks, dw.data_ptr() if dw is not None else None,
-                                               db.data_ptr() if db is not None else None, _C._stream_ptr(dev)))
+        ws = _workspace(L.gsr_deform_in_workspace_bytes(P, H, ctx.max_blocks), dev)
+        _call(dev, L.gsr_deform_in_backward, P, H, im.data_ptr(), iq.data_ptr(), ir.data_ptr(), pm.data_ptr(),
+              pq.data_ptr(), pr.data_ptr(), ctx.progress, g.data_ptr(), ws.data_ptr(), ctx.max_blocks, _ptr(dw),
+              _ptr(db))
         return (dw, db) + (None,) * 9
 
 
@@ -150,8 +186,7 @@ def deform_input_layer(weight, bias, initial_params, previous_params, progress, 
     pm, pq = _means_and_rotations(previous_params, "deform_input_layer (previous)")
     if pm.shape[0] != im.shape[0]:
         raise ValueError(f"deform_input_layer: {im.shape[0]} initial and {pm.shape[0]} previous Gaussians")
-    if max_blocks < 0:
-        raise ValueError("deform_input_layer: max_blocks must be >= 0")
+    _check_blocks(max_blocks, "deform_input_layer")
     _need_gpu("weight, bias and params", weight, bias, im, iq, pm, pq)
     ir, pr = encoding_ranges(im, iq), encoding_ranges(pm, pq)
     # the reference builds the scalar as torch.tensor(timestep / timestep_count): rounded to fp32 once
@@ -174,19 +209,15 @@ def set_fused_residual_blocks(on):
 class _ResBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, g1, b1, w2, g2, b2, bn1, bn2, max_blocks, save):
-        L = _C.resblock_library()
+        L = _C.feature_library("resblock")
         P, H, dev = x.shape[0], x.shape[1], x.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731 - every element is written
         y1, y2, out, stats = new(P, H), new(P, H), new(P, H), new(4 * H)
-        ws = torch.empty(max(L.gsr_resblock_workspace_bytes(P, H, max_blocks, 0), 1), dtype=torch.uint8, device=dev)
-        running = [t.data_ptr() if t is not None else None
-                   for t in (bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var)]
-        with _C._device_guard(dev):
-            _C._check(L.gsr_resblock_forward(P, H, x.data_ptr(), w1.data_ptr(), g1.data_ptr(), b1.data_ptr(),
-                                             w2.data_ptr(), g2.data_ptr(), b2.data_ptr(), bn1.eps, bn2.eps,
-                                             bn1.momentum, bn2.momentum, *running, ws.data_ptr(), max_blocks,
-                                             y1.data_ptr(), y2.data_ptr(), out.data_ptr(), stats.data_ptr(),
-                                             _C._stream_ptr(dev)))
+        ws = _workspace(L.gsr_resblock_workspace_bytes(P, H, max_blocks, 0), dev)
+        running = [_ptr(t) for t in (bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var)]
+        _call(dev, L.gsr_resblock_forward, P, H, x.data_ptr(), w1.data_ptr(), g1.data_ptr(), b1.data_ptr(),
+              w2.data_ptr(), g2.data_ptr(), b2.data_ptr(), bn1.eps, bn2.eps, bn1.momentum, bn2.momentum, *running,
+              ws.data_ptr(), max_blocks, y1.data_ptr(), y2.data_ptr(), out.data_ptr(), stats.data_ptr())
         if save:
             ctx.save_for_backward(x, y1, y2, stats, w1, g1, b1, w2, g2, b2)
             ctx.max_blocks = max_blocks
@@ -195,19 +226,16 @@ class _ResBlock(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        L = _C.resblock_library()
+        L = _C.feature_library("resblock")
         x, y1, y2, stats, w1, g1, b1, w2, g2, b2 = ctx.saved_tensors
         P, H, dev = x.shape[0], x.shape[1], x.device
         g = g.contiguous().float()
         grads = [torch.empty_like(t) if need else None
                  for t, need in zip((x, w1, g1, b1, w2, g2, b2), ctx.needs_input_grad[:7])]
-        ws = torch.empty(max(L.gsr_resblock_workspace_bytes(P, H, ctx.max_blocks, 1), 1), dtype=torch.uint8, device=dev)
-        with _C._device_guard(dev):
-            _C._check(L.gsr_resblock_backward(P, H, x.data_ptr(), y1.data_ptr(), y2.data_ptr(), stats.data_ptr(),
-                                              w1.data_ptr(), g1.data_ptr(), b1.data_ptr(), w2.data_ptr(), g2.data_ptr(),
-                                              b2.data_ptr(), g.data_ptr(), ws.data_ptr(), ctx.max_blocks,
-                                              *[t.data_ptr() if t is not None else None for t in grads],
-                                              _C._stream_ptr(dev)))
+        ws = _workspace(L.gsr_resblock_workspace_bytes(P, H, ctx.max_blocks, 1), dev)
+        _call(dev, L.gsr_resblock_backward, P, H, x.data_ptr(), y1.data_ptr(), y2.data_ptr(), stats.data_ptr(),
+              w1.data_ptr(), g1.data_ptr(), b1.data_ptr(), w2.data_ptr(), g2.data_ptr(), b2.data_ptr(), g.data_ptr(),
+              ws.data_ptr(), ctx.max_blocks, *[_ptr(t) for t in grads])
         return tuple(grads) + (None,) * 4
 
 
@@ -229,11 +257,7 @@ def residual_block(x, fc1_weight, bn1, fc2_weight, bn2, max_blocks=0):
     ``num_batches_tracked`` incremented as ``F.batch_norm`` does.  Gradients flow to ``x``, both weights and
     both BatchNorms' affine parameters; the graph keeps ``x``, the two GEMM outputs and 4 H statistics.
     ``max_blocks``: upper bound on the persistent workgroups (0: automatic)."""
-    if x.dim() != 2 or x.dtype != torch.float32:
-        raise ValueError(f"residual_block: x {tuple(x.shape)} {x.dtype}, expected float32 (P, H)")
-    P, H = x.shape
-    if not 1 <= H <= MAX_FUSED_HIDDEN:
-        raise ValueError(f"residual_block: hidden dimension {H} outside [1, {MAX_FUSED_HIDDEN}]")
+    P, H = _check_activation(x, "residual_block", MAX_FUSED_HIDDEN)
     if P < 2:
         raise ValueError(f"residual_block: batch statistics need more than one row (got {P})")
     for w, name in ((fc1_weight, "fc1_weight"), (fc2_weight, "fc2_weight")):
@@ -241,8 +265,7 @@ def residual_block(x, fc1_weight, bn1, fc2_weight, bn2, max_blocks=0):
             raise ValueError(f"residual_block: {name} {tuple(w.shape)} {w.dtype}, expected float32 ({H}, {H})")
     _check_bn(bn1, H, "bn1")
     _check_bn(bn2, H, "bn2")
-    if max_blocks < 0:
-        raise ValueError("residual_block: max_blocks must be >= 0")
+    _check_blocks(max_blocks, "residual_block")
     params = (fc1_weight, bn1.weight, bn1.bias, fc2_weight, bn2.weight, bn2.bias)
     _need_gpu("x, the weights and the BatchNorms", x, *params,
               *(t for bn in (bn1, bn2) for t in (bn.running_mean, bn.running_var) if t is not None))
@@ -268,8 +291,8 @@ class ResidualBlock(nn.Module):
         self.bn2 = nn.BatchNorm1d(dimension)
 
     def _fused(self, x):
-        if not (_FUSED_RESBLOCKS and self.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
-                and x.is_contiguous() and x.shape[0] >= 2 and x.shape[1] <= MAX_FUSED_HIDDEN):
+        if not (_FUSED_RESBLOCKS and self.training and x.dim() == 2 and x.shape[0] >= 2
+                and x.shape[1] <= MAX_FUSED_HIDDEN):
             return False
         if tuple(self.fc1.weight.shape) != (x.shape[1],) * 2 or tuple(self.fc2.weight.shape) != (x.shape[1],) * 2:
             return False
@@ -277,9 +300,9 @@ class ResidualBlock(nn.Module):
             if not (isinstance(bn, nn.BatchNorm1d) and bn.affine and bn.track_running_stats and bn.momentum is not None
                     and bn.running_mean is not None):
                 return False
-        return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (
-            self.fc1.weight, self.fc2.weight, self.bn1.weight, self.bn1.bias, self.bn2.weight, self.bn2.bias,
-            self.bn1.running_mean, self.bn1.running_var, self.bn2.running_mean, self.bn2.running_var))
+        params = (self.fc1.weight, self.fc2.weight, self.bn1.weight, self.bn1.bias, self.bn2.weight, self.bn2.bias,
+                  self.bn1.running_mean, self.bn1.running_var, self.bn2.running_mean, self.bn2.running_var)
+        return _eligible(x, *params) and all(t.is_contiguous() for t in params)
 
     def forward(self, x):
         if self._fused(x):
@@ -306,14 +329,13 @@ def set_fused_output_head(on):
 class _DeformOut(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, means, quats, max_blocks, save):
-        L = _C.head_library()
+        L = _C.feature_library("head")
         x, w, b = x.detach().contiguous(), weight.detach().contiguous(), bias.detach().contiguous()
         im, iq = means.detach().contiguous(), quats.detach().contiguous()
         P, H, dev = x.shape[0], x.shape[1], x.device
         out = torch.empty((P, 7), dtype=torch.float32, device=dev)
-        with _C._device_guard(dev):
-            _C._check(L.gsr_deform_out_forward(P, H, x.data_ptr(), w.data_ptr(), b.data_ptr(), im.data_ptr(),
-                                               iq.data_ptr(), out.data_ptr(), _C._stream_ptr(dev)))
+        _call(dev, L.gsr_deform_out_forward, P, H, x.data_ptr(), w.data_ptr(), b.data_ptr(), im.data_ptr(),
+              iq.data_ptr(), out.data_ptr())
         ctx.saved = save
         if save:
             ctx.save_for_backward(x, w)
@@ -329,7 +351,7 @@ class _DeformOut(torch.autograd.Function):
         gq = g[:, 3:] if need[4] else None
         if not ctx.saved or not any(need[:3]):
             return None, None, None, gm, gq, None, None
-        L = _C.head_library()
+        L = _C.feature_library("head")
         x, w = ctx.saved_tensors
         P, H, dev = x.shape[0], x.shape[1], x.device
         g = g.contiguous().float()
@@ -337,12 +359,9 @@ class _DeformOut(torch.autograd.Function):
         dw = torch.empty_like(w) if need[1] else None
         db = torch.empty((7,), dtype=torch.float32, device=dev) if need[2] else None
         sums = dw is not None or db is not None
-        ws = torch.empty(max(L.gsr_deform_out_workspace_bytes(P, H, ctx.max_blocks), 1) if sums else 1,
-                         dtype=torch.uint8, device=dev)
-        with _C._device_guard(dev):
-            _C._check(L.gsr_deform_out_backward(P, H, x.data_ptr(), w.data_ptr(), g.data_ptr(), ws.data_ptr(),
-                                                ctx.max_blocks, *[t.data_ptr() if t is not None else None
-                                                                  for t in (dx, dw, db)], _C._stream_ptr(dev)))
+        ws = _workspace(L.gsr_deform_out_workspace_bytes(P, H, ctx.max_blocks) if sums else 0, dev)
+        _call(dev, L.gsr_deform_out_backward, P, H, x.data_ptr(), w.data_ptr(), g.data_ptr(), ws.data_ptr(),
+              ctx.max_blocks, _ptr(dx), _ptr(dw), _ptr(db))
         return dx, dw, db, gm, gq, None, None
 
 
@@ -354,24 +373,13 @@ def deform_output_layer(x, weight, bias, initial_params, max_blocks=0):
     and quaternions when they require one (the upstream gradient's columns, as from ``out + torch.cat(...)``);
     the graph keeps ``x`` and ``weight``.  ``max_blocks``: upper bound on the backward's persistent workgroups
     (0: automatic)."""
-    if x.dim() != 2 or x.dtype != torch.float32:
-        raise ValueError(f"deform_output_layer: x {tuple(x.shape)} {x.dtype}, expected float32 (P, H)")
-    P, H = x.shape
-    if not 1 <= H <= MAX_HIDDEN:
-        raise ValueError(f"deform_output_layer: hidden dimension {H} outside [1, {MAX_HIDDEN}]")
+    P, H = _check_activation(x, "deform_output_layer", MAX_HIDDEN)
     if tuple(weight.shape) != (7, H) or weight.dtype != torch.float32:
         raise ValueError(f"deform_output_layer: weight {tuple(weight.shape)} {weight.dtype}, expected float32 (7, {H})")
     if tuple(bias.shape) != (7,) or bias.dtype != torch.float32:
         raise ValueError(f"deform_output_layer: bias {tuple(bias.shape)} {bias.dtype}, expected float32 (7,)")
-    means, quats = initial_params["means"], initial_params["rotation_quaternions"]
-    if tuple(means.shape) != (P, 3) or tuple(quats.shape) != (P, 4):
-        raise ValueError(f"deform_output_layer: means {tuple(means.shape)} / rotation_quaternions "
-                         f"{tuple(quats.shape)}, expected ({P}, 3) / ({P}, 4)")
-    for t in (means, quats):
-        if t.dtype != torch.float32:
-            raise ValueError(f"deform_output_layer: expected float32 parameters, got {t.dtype}")
-    if max_blocks < 0:
-        raise ValueError("deform_output_layer: max_blocks must be >= 0")
+    means, quats = _param_tensors(initial_params, "deform_output_layer", P)  # attached: gradients reach them
+    _check_blocks(max_blocks, "deform_output_layer")
     _need_gpu("x, weight, bias and params", x, weight, bias, means, quats)
     save = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or bias.requires_grad)
     return _DeformOut.apply(x, weight, bias, means, quats, int(max_blocks), save)
@@ -393,11 +401,9 @@ class DeformationNetwork(nn.Module):
         self.fc_out = nn.Linear(hidden_dimension, 7)
 
     def _fused_head(self, x):
-        if not (_FUSED_HEAD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()):
-            return False
         w, b = self.fc_out.weight, self.fc_out.bias
-        return (b is not None and tuple(w.shape) == (7, x.shape[1]) and x.shape[1] <= MAX_HIDDEN
-                and all(t.is_cuda and t.dtype == torch.float32 for t in (w, b)))
+        return (_FUSED_HEAD and b is not None and _eligible(x, w, b) and tuple(w.shape) == (7, x.shape[1])
+                and x.shape[1] <= MAX_HIDDEN)
 
     def forward(self, initial_params, previous_params, timestep, timestep_count):
         out = deform_input_layer(self.fc_in.weight, self.fc_in.bias, initial_params, previous_params,

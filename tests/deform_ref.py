@@ -5,9 +5,34 @@ The encoding is parameterised by dtype.  ``torch.float32`` uses the reference's 
 arguments (its result equals the reference's bit for bit on the same device); ``torch.float64`` starts
 from the SAME fp32 arguments ``f_l * xn`` (the normalisation and the product stay fp32: they are part of
 the definition) and evaluates the sine and the cosine of it in float64.
+
+``band`` and ``yardstick`` are the comparisons the three test files of the network share.
 """
+import numpy as np
 import torch
 from torch import nn
+
+
+def band(name, got, ref, rtol=1e-4, atol_frac=1e-6, floor=0.0):
+    """|got - ref| <= max(rtol |ref| + atol_frac max|ref|, floor) everywhere, both finite."""
+    got = np.asarray(got.detach().cpu() if torch.is_tensor(got) else got, np.float64)
+    ref = np.asarray(ref.detach().cpu() if torch.is_tensor(ref) else ref, np.float64)
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    assert np.isfinite(ref).all() and np.isfinite(got).all(), name
+    scale = np.abs(ref).max()
+    err = np.abs(got - ref)
+    bad = err > np.maximum(rtol * np.abs(ref) + atol_frac * scale, floor)
+    print(f"{name}: worst {err.max():.3e} = {err.max() / max(scale, 1e-300):.3e} max|ref| ({scale:.3e}), "
+          f"floor {floor:.3e}, outside {bad.sum()}/{bad.size}")
+    assert not bad.any(), f"{name}: {bad.sum()}/{bad.size} outside the band, worst {err.max():.3g} (scale {scale:.3g})"
+
+
+def yardstick(name, got, r32, r64):
+    """``band`` against the float64 result, never tighter than twice what torch's own float32 composition misses
+    it by."""
+    yard = float((r32.double() - r64).abs().max()) if r64.numel() else 0.0
+    print(f"{name}: float32 torch composition vs float64 {yard:.3e}")
+    band(name, got, r64, floor=2 * yard)
 
 
 def normalize(x):

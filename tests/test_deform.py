@@ -15,6 +15,8 @@ import torch
 
 import deform_ref as DR
 import splat_deform as D
+from deform_ref import band
+from diff_gaussian_rasterization import _C
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = np.load(os.path.join(HERE, "golden", "reference_deform.npz"))
@@ -38,19 +40,6 @@ def _gold_progress():
 
 def _gold_state():
     return {str(n): _t(f"state/{n}") for n in GOLD["state_names"]}
-
-
-def _band(name, got, ref, rtol=1e-4, atol_frac=1e-6, floor=0.0):
-    got = np.asarray(got.detach().cpu() if torch.is_tensor(got) else got, np.float64)
-    ref = np.asarray(ref.detach().cpu() if torch.is_tensor(ref) else ref, np.float64)
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    assert np.isfinite(ref).all() and np.isfinite(got).all(), name
-    scale = np.abs(ref).max()
-    err = np.abs(got - ref)
-    bad = err > np.maximum(rtol * np.abs(ref) + atol_frac * scale, floor)
-    print(f"{name}: worst {err.max():.3e} = {err.max() / max(scale, 1e-300):.3e} max|ref| ({scale:.3e}), "
-          f"floor {floor:.3e}, outside {bad.sum()}/{bad.size}")
-    assert not bad.any(), f"{name}: {bad.sum()}/{bad.size} outside the band, worst {err.max():.3g} (scale {scale:.3g})"
 
 
 @functools.lru_cache(maxsize=None)
@@ -104,20 +93,38 @@ def test_network_restatement_reproduces_reference():
     net.train()
     out, fc_in_out, grads = DR.network_output_and_grads(net, initial, previous, _gold_progress(), _t("upstream"),
                                                         torch.float32)
-    _band("fc_in_output", fc_in_out, GOLD["fc_in_output"], 2e-4, 2e-5)
-    _band("output", out, GOLD["output"], 2e-4, 2e-5)
+    band("fc_in_output", fc_in_out, GOLD["fc_in_output"], 2e-4, 2e-5)
+    band("output", out, GOLD["output"], 2e-4, 2e-5)
     for name, g in grads.items():
-        _band(f"grad {name}", g, GOLD[f"grad/{name}"], 2e-4, 2e-5)
+        band(f"grad {name}", g, GOLD[f"grad/{name}"], 2e-4, 2e-5)
 
 
-def test_stale_library_is_a_rebuild_error(monkeypatch):
-    """A libgsr.so without the entry points raises on first use of the feature, naming the remedy."""
-    from diff_gaussian_rasterization import _C
-    _C.load_library()
-    assert _C._DEFORM_MISSING is None and _C.deform_library() is _C.load_library()
-    monkeypatch.setattr(_C, "_DEFORM_MISSING", "undefined symbol: gsr_deform_in_forward")
+FEATURES = ("deform", "resblock", "head")
+
+
+@pytest.mark.parametrize("feature", FEATURES)
+def test_stale_library_is_a_rebuild_error(monkeypatch, feature):
+    """A libgsr.so without one feature's entry points still loads and serves everything else; that feature
+    raises on first use, naming the remedy."""
+    real = _C.load_library()
+    assert not _C._MISSING and _C.feature_library(feature) is real
+    absent = list(_C._OPTIONAL[feature][1])
+
+    class Stale:
+        def __getattr__(self, name):
+            if name in absent:
+                raise AttributeError(f"undefined symbol: {name}")
+            return getattr(real, name)
+
+    monkeypatch.setattr(_C, "_lib", None)
+    monkeypatch.setattr(_C, "_MISSING", {})
+    monkeypatch.setattr(_C, "_PREALLOC_FN", _C._PREALLOC_FN)
+    monkeypatch.setattr(_C.ctypes, "CDLL", lambda path: Stale())
+    stale = _C.load_library()
+    assert isinstance(stale, Stale) and list(_C._MISSING) == [feature] and absent[0] in _C._MISSING[feature]
+    assert all(_C.feature_library(other) is stale for other in FEATURES if other != feature)
     with pytest.raises(RuntimeError, match="rebuild"):
-        _C.deform_library()
+        _C.feature_library(feature)
 
 
 def test_module_contract():
@@ -201,7 +208,7 @@ def test_fused_forward(cuda, P, H):
     initial, previous, w, b, _, x64 = _layer_case(cuda, P, H)
     got = D.deform_input_layer(w, b, initial, previous, PROGRESS)
     assert got.shape == (P, H) and got.dtype == torch.float32
-    _band(f"fc_in output ({P}, {H})", got, x64 @ w.double().t() + b.double())
+    band(f"fc_in output ({P}, {H})", got, x64 @ w.double().t() + b.double())
 
 
 @pytest.mark.gpu
@@ -214,10 +221,10 @@ def test_fused_backward(cuda, P, H, max_blocks):
     w, b = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
     out = D.deform_input_layer(w, b, initial, previous, PROGRESS, max_blocks=max_blocks)
     out.backward(up)
-    _band(f"dW ({P}, {H}, max_blocks={max_blocks})", w.grad, up.double().t() @ x64)
-    _band(f"db ({P}, {H}, max_blocks={max_blocks})", b.grad, up.double().sum(0))
+    band(f"dW ({P}, {H}, max_blocks={max_blocks})", w.grad, up.double().t() @ x64)
+    band(f"db ({P}, {H}, max_blocks={max_blocks})", b.grad, up.double().sum(0))
     pe64 = DR.encode_progress(PROGRESS, 1, cuda, torch.float64)[0]
-    _band("dW[:, 184:] = enc(progress) db", w.grad[:, 184:], b.grad.double()[:, None] * pe64[None, :])
+    band("dW[:, 184:] = enc(progress) db", w.grad[:, 184:], b.grad.double()[:, None] * pe64[None, :])
     for cloud in (initial, previous):
         assert all(v.grad is None for v in cloud.values())  # the encoded parameters are detached
 
@@ -228,10 +235,10 @@ def test_golden_fc_in(cuda):
     w = _t("state/fc_in.weight").to(cuda).requires_grad_(True)
     b = _t("state/fc_in.bias").to(cuda).requires_grad_(True)
     out = D.deform_input_layer(w, b, initial, previous, _gold_progress())
-    _band("golden fc_in output", out, GOLD["fc_in_output"], 2e-4, 2e-5)
+    band("golden fc_in output", out, GOLD["fc_in_output"], 2e-4, 2e-5)
     out.backward(_t("grad_fc_in_output").to(cuda))  # the gradient that reached fc_in's output in the reference
-    _band("golden grad fc_in.weight", w.grad, GOLD["grad/fc_in.weight"], 2e-4, 2e-5)
-    _band("golden grad fc_in.bias", b.grad, GOLD["grad/fc_in.bias"], 2e-4, 2e-5)
+    band("golden grad fc_in.weight", w.grad, GOLD["grad/fc_in.weight"], 2e-4, 2e-5)
+    band("golden grad fc_in.bias", b.grad, GOLD["grad/fc_in.bias"], 2e-4, 2e-5)
 
 
 # ---- GPU: the whole network -----------------------------------------------------------------------
@@ -272,7 +279,7 @@ def test_whole_network(cuda):
 
     def check(name, got, r32, r64):
         yard = float((r32.double() - r64).abs().max())
-        _band(name, got, r64, floor=2 * yard)
+        band(name, got, r64, floor=2 * yard)
 
     check("updated means and quaternions", y, y32, y64)
     for name, p in fused.named_parameters():

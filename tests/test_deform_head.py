@@ -1,7 +1,7 @@
 """The deformation network's output head (splat_deform.deform_output_layer, csrc/gsr_head.hip): fc_out and the
 ``+ [initial means | initial quaternions]`` update in one kernel, with its backward.
 
-CPU: the exports, the argument validation, the stale-library error, the untouched state_dict and torch lines.
+CPU: the exports, the argument validation, the untouched state_dict and torch lines.
 GPU: the kernels against the float64 restatement.  The yardstick is the float32 torch composition's own worst
 error against float64 on the same device and inputs; the kernel may have the project band
 (1e-4 |ref| + 1e-6 max|ref|) or twice that yardstick, whichever is larger.  "Golden band": 2e-4 |ref| +
@@ -12,36 +12,17 @@ import functools
 import itertools
 import os
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import deform_ref as DR
 import splat_deform as D
+from deform_ref import band, yardstick
 from diff_gaussian_rasterization import _C
 from test_deform import GOLD, _clouds, _gold_clouds, _gold_progress, _gold_state, _t, _to
 
 CASES = [(1, 64), (63, 64), (65, 1), (130, 129), (257, 128), (1031, 7), (1031, 40), (4099, 64), (257, 512)]
-
-
-def _band(name, got, ref, rtol=1e-4, atol_frac=1e-6, floor=0.0):
-    got = np.asarray(got.detach().cpu() if torch.is_tensor(got) else got, np.float64)
-    ref = np.asarray(ref.detach().cpu() if torch.is_tensor(ref) else ref, np.float64)
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    assert np.isfinite(ref).all() and np.isfinite(got).all(), name
-    scale = np.abs(ref).max()
-    err = np.abs(got - ref)
-    bad = err > np.maximum(rtol * np.abs(ref) + atol_frac * scale, floor)
-    print(f"{name}: worst {err.max():.3e} = {err.max() / max(scale, 1e-300):.3e} max|ref| ({scale:.3e}), "
-          f"floor {floor:.3e}, outside {bad.sum()}/{bad.size}")
-    assert not bad.any(), f"{name}: {bad.sum()}/{bad.size} outside the band, worst {err.max():.3g} (scale {scale:.3g})"
-
-
-def _check(name, got, r32, r64):
-    yard = float((r32.double() - r64).abs().max()) if r64.numel() else 0.0
-    print(f"{name}: float32 torch composition vs float64 {yard:.3e}")
-    _band(name, got, r64, floor=2 * yard)
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,29 +96,6 @@ def test_contract():
     assert D.set_fused_output_head(first) is first
 
 
-def test_stale_library_is_a_rebuild_error(monkeypatch):
-    """A libgsr.so without the head's entry points still loads and serves everything else; the head raises
-    on first use, naming the remedy."""
-    real = _C.load_library()
-    assert _C._HEAD_MISSING is None and _C.head_library() is real
-
-    class Stale:
-        def __getattr__(self, name):
-            if name.startswith("gsr_deform_out_"):
-                raise AttributeError(f"undefined symbol: {name}")
-            return getattr(real, name)
-
-    monkeypatch.setattr(_C, "_lib", None)
-    monkeypatch.setattr(_C, "_HEAD_MISSING", None)
-    monkeypatch.setattr(_C, "_PREALLOC_FN", _C._PREALLOC_FN)
-    monkeypatch.setattr(_C.ctypes, "CDLL", lambda path: Stale())
-    stale = _C.load_library()
-    assert isinstance(stale, Stale) and "gsr_deform_out_forward" in _C._HEAD_MISSING
-    assert _C.deform_library() is stale and _C.resblock_library() is stale
-    with pytest.raises(RuntimeError, match="rebuild"):
-        _C.head_library()
-
-
 def test_state_dict_and_torch_lines_untouched(monkeypatch):
     net = D.DeformationNetwork(32, 1)
     state = net.state_dict()
@@ -173,7 +131,7 @@ def test_forward(cuda, P, H):
     x, w, b, _, initial, r32, r64 = _case(P, H)
     got = D.deform_output_layer(x, w, b, initial)
     assert got.shape == (P, 7) and got.dtype == torch.float32
-    _check(f"output ({P}, {H})", got, r32["out"], r64["out"])
+    yardstick(f"output ({P}, {H})", got, r32["out"], r64["out"])
 
 
 @pytest.mark.gpu
@@ -182,10 +140,10 @@ def test_backward(cuda, P, H, max_blocks):
     x, w, b, up, initial, r32, r64 = _case(P, H)
     out, dx, dw, db = _run(x, w, b, up, initial, max_blocks)
     tag = f"({P}, {H}, max_blocks={max_blocks})"
-    _check(f"output {tag}", out, r32["out"], r64["out"])
-    _check(f"dx {tag}", dx, r32["dx"], r64["dx"])
-    _check(f"dW {tag}", dw, r32["dw"], r64["dw"])
-    _check(f"db {tag}", db, r32["db"], r64["db"])
+    yardstick(f"output {tag}", out, r32["out"], r64["out"])
+    yardstick(f"dx {tag}", dx, r32["dx"], r64["dx"])
+    yardstick(f"dW {tag}", dw, r32["dw"], r64["dw"])
+    yardstick(f"db {tag}", db, r32["db"], r64["db"])
     assert all(v.grad is None for v in initial.values())
 
 
@@ -233,7 +191,7 @@ def test_null_dx_writes_nothing_of_that_size(cuda):
     read) and the result is the same."""
     P, H = 1031, 40
     x, w, b, up, initial, _, _ = _case(P, H)
-    L = _C.head_library()
+    L = _C.feature_library("head")
     full = _run(x, w, b, up, initial, 2)
     sentinel = torch.full((P, H), float("nan"), device=cuda)
     sentinel.view(torch.int32).fill_(0x7FC12345)
@@ -305,9 +263,9 @@ def test_golden(cuda):
     out = net(initial, previous, timestep, count)
     assert type(out.grad_fn).__name__ == "_DeformOutBackward"
     out.backward(_t("upstream").to(cuda))
-    _band("golden output", out, GOLD["output"], 2e-4, 2e-5)
+    band("golden output", out, GOLD["output"], 2e-4, 2e-5)
     for name in ("fc_out.weight", "fc_out.bias", "fc_in.weight"):
-        _band(f"golden grad {name}", net.get_parameter(name).grad, GOLD[f"grad/{name}"], 2e-4, 2e-5)
+        band(f"golden grad {name}", net.get_parameter(name).grad, GOLD[f"grad/{name}"], 2e-4, 2e-5)
 
 
 @pytest.mark.gpu
@@ -354,7 +312,7 @@ def test_routing(cuda):
 
     def close(name, a, c, r32, r64):  # the two legs differ by no more than the band around either
         yard = float((r32.double() - r64).abs().max())
-        _band(name, a, c, floor=2 * yard)
+        band(name, a, c, floor=2 * yard)
 
     close("output on vs off", out_on, out_off, o32, o64)
     for n in names:

@@ -20,28 +20,12 @@ from torch import nn
 
 import deform_ref as DR
 import splat_deform as D
+from deform_ref import band, yardstick
 from diff_gaussian_rasterization import _C
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = np.load(os.path.join(HERE, "golden", "reference_deform.npz"))
 PARAMS = ("fc1.weight", "bn1.weight", "bn1.bias", "fc2.weight", "bn2.weight", "bn2.bias")
-
-
-def _band(name, got, ref, rtol=1e-4, atol_frac=1e-6, floor=0.0):
-    got = np.asarray(got.detach().cpu() if torch.is_tensor(got) else got, np.float64)
-    ref = np.asarray(ref.detach().cpu() if torch.is_tensor(ref) else ref, np.float64)
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    assert np.isfinite(ref).all() and np.isfinite(got).all(), name
-    scale = np.abs(ref).max()
-    err = np.abs(got - ref)
-    bad = err > np.maximum(rtol * np.abs(ref) + atol_frac * scale, floor)
-    print(f"{name}: worst {err.max():.3e} = {err.max() / max(scale, 1e-300):.3e} max|ref| ({scale:.3e}), "
-          f"floor {floor:.3e}, outside {bad.sum()}/{bad.size}")
-    assert not bad.any(), f"{name}: {bad.sum()}/{bad.size} outside the band, worst {err.max():.3g} (scale {scale:.3g})"
-
-
-def _yardstick(name, got, r32, r64):
-    _band(name, got, r64, floor=2 * float((r32.double() - r64).abs().max()))
 
 
 def _torch_lines(block, x):
@@ -122,9 +106,9 @@ def _fused(device, P, H, offset=False, momentum=None, max_blocks=0, calls=1, nee
 
 
 def _check_all(tag, got, r32, r64):
-    _yardstick(f"{tag} out", got[0], r32[0], r64[0])
+    yardstick(f"{tag} out", got[0], r32[0], r64[0])
     for name in ("x",) + PARAMS:
-        _yardstick(f"{tag} grad {name}", got[1][name], r32[1][name], r64[1][name])
+        yardstick(f"{tag} grad {name}", got[1][name], r32[1][name], r64[1][name])
 
 
 # ---- CPU ------------------------------------------------------------------------------------------
@@ -157,15 +141,6 @@ def test_torch_path_bit_for_bit():
         D.residual_block(x, b.fc1.weight, b.bn1, b.fc2.weight, b.bn2)
 
 
-def test_stale_library_is_a_rebuild_error(monkeypatch):
-    """A libgsr.so without the entry points raises on first use of the feature, naming the remedy."""
-    _C.load_library()
-    assert _C._RESBLOCK_MISSING is None and _C.resblock_library() is _C.load_library()
-    monkeypatch.setattr(_C, "_RESBLOCK_MISSING", "undefined symbol: gsr_resblock_forward")
-    with pytest.raises(RuntimeError, match="rebuild"):
-        _C.resblock_library()
-
-
 # ---- GPU ------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("max_blocks", [0, 2])
@@ -185,8 +160,8 @@ def test_running_statistics(cuda, P, H):
         block = _fused(cuda, P, H, calls=calls)[2]
         for bn, ref in ((block.bn1, want.bn1), (block.bn2, want.bn2)):
             assert int(bn.num_batches_tracked) == calls == int(ref.num_batches_tracked)
-            _band(f"running_mean after {calls}", bn.running_mean, ref.running_mean)
-            _band(f"running_var after {calls}", bn.running_var, ref.running_var)
+            band(f"running_mean after {calls}", bn.running_mean, ref.running_mean)
+            band(f"running_var after {calls}", bn.running_var, ref.running_var)
 
 
 @pytest.mark.gpu
@@ -196,8 +171,8 @@ def test_stable_variance(cuda, P, H):
     sum-of-squares variance is off by tens of percent and a shifted one is within 1e-5."""
     r32, r64 = _reference(cuda, P, H, offset=True, momentum=1.0)
     got = _fused(cuda, P, H, offset=True, momentum=1.0)
-    _band("bn1.running_mean", got[2].bn1.running_mean, r64[2].bn1.running_mean)
-    _band("bn1.running_var", got[2].bn1.running_var, r64[2].bn1.running_var)
+    band("bn1.running_mean", got[2].bn1.running_mean, r64[2].bn1.running_mean)
+    band("bn1.running_var", got[2].bn1.running_var, r64[2].bn1.running_var)
     _check_all(f"offset ({P}, {H})", got, r32, r64)
 
 
@@ -213,11 +188,11 @@ def test_golden_network(cuda):
     timestep, count = (int(v) for v in GOLD["timestep"])
     out = net(initial, previous, timestep, count)
     (out * t("upstream")).sum().backward()
-    _band("golden output", out, GOLD["output"], 2e-4, 2e-5)
+    band("golden output", out, GOLD["output"], 2e-4, 2e-5)
     names = [n for n, _ in net.named_parameters()]
     assert any(n.startswith("residual_blocks.0.") for n in names)
     for n, p in net.named_parameters():
-        _band(f"golden grad {n}", p.grad, GOLD[f"grad/{n}"], 2e-4, 2e-5)
+        band(f"golden grad {n}", p.grad, GOLD[f"grad/{n}"], 2e-4, 2e-5)
 
 
 @pytest.mark.gpu
@@ -310,7 +285,7 @@ def test_two_blocks_chained(cuda):
         return out.detach(), {"x": xd.grad, **{n: p.grad for n, p in net.named_parameters()}}
 
     r64, r32, got = run(DR.ResidualBlock, torch.float64), run(DR.ResidualBlock, torch.float32), run(D.ResidualBlock, torch.float32)
-    _yardstick("chained out", got[0], r32[0], r64[0])
+    yardstick("chained out", got[0], r32[0], r64[0])
     assert set(got[1]) == set(r64[1]) and len(got[1]) == 13
     for name in got[1]:
-        _yardstick(f"chained grad {name}", got[1][name], r32[1][name], r64[1][name])
+        yardstick(f"chained grad {name}", got[1][name], r32[1][name], r64[1][name])
