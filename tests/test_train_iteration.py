@@ -15,22 +15,10 @@ import pytest
 import torch
 
 from test_gpu_parity import STATS
+from train_ref import torch_ssim as _torch_ssim  # in the images' dtype: float32 here, as before
 
 ORDER = ["means", "colors", "segmentation_masks", "rotation_quaternions", "opacity_logits", "log_scales",
          "camera_matrices", "camera_center"]
-
-
-def _torch_ssim(img1, img2):
-    from math import exp
-    g = torch.tensor([exp(-((x - 5) ** 2) / float(2 * 1.5 ** 2)) for x in range(11)])
-    g = (g / g.sum()).unsqueeze(1)
-    C = img1.size(-3)
-    w = g.mm(g.t()).float()[None, None].expand(C, 1, 11, 11).contiguous().to(img1.device)
-    conv = lambda t: torch.nn.functional.conv2d(t, w, padding=5, groups=C)  # noqa: E731
-    mu1, mu2 = conv(img1), conv(img2)
-    s1, s2, s12 = conv(img1 * img1) - mu1 ** 2, conv(img2 * img2) - mu2 ** 2, conv(img1 * img2) - mu1 * mu2
-    c1, c2 = 0.01 ** 2, 0.03 ** 2
-    return (((2 * mu1 * mu2 + c1) * (2 * s12 + c2)) / ((mu1 ** 2 + mu2 ** 2 + c1) * (s1 + s2 + c2))).mean()
 
 
 @pytest.mark.gpu
