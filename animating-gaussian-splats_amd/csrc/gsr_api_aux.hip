@@ -66,6 +66,12 @@ int check_rigid(int P, int F, int k) {
     if ((size_t)F * (size_t)k >= (size_t)1 << 31) return fail(GSR_ERR_UNSUPPORTED, "rigidity: more than 2^31 edges");
     return GSR_OK;
 }
+// the entry points that write a foreground state: a non-empty foreground and the neighbour search's k
+int check_foreground(int P, int F, int k) {
+    if (F <= 0) return fail(GSR_ERR_ARG, "foreground_info: F must be > 0 (got %d)", F);
+    if (k < 1 || k > kKnnMaxK) return fail(GSR_ERR_ARG, "foreground_info: k = %d (1 to %d supported)", k, kKnnMaxK);
+    return check_rigid(P, F, k);
+}
 
 // the deformation network's units: `what` is deform_in, resblock or deform_out
 int check_blocks(const char *what, int max_blocks) {
@@ -158,10 +164,11 @@ size_t gsr_rigidity_scratch_bytes(int F, int k, int save_for_backward) {
     return RigidScratch(F < 0 ? 0 : F, k < 0 ? 0 : k, save_for_backward != 0).total;
 }
 
-int gsr_rigidity_forward(int P, int F, int k, const float *means, const float *rotation_quaternions,
-                         const int *foreground_rows, const int *neighbor_rows, const float *weights,
-                         const float *previous_offsets, const float *previous_inverted_rotations, void *scratch,
-                         int save_for_backward, float *out_loss, void *stream) {
+// gsr_rigidity_forward, and with next_* (both) gsr_rigidity_forward_state
+static int rigidity_forward(int P, int F, int k, const float *means, const float *rotation_quaternions,
+                            const int *foreground_rows, const int *neighbor_rows, const float *weights,
+                            const float *previous_offsets, const float *previous_inverted_rotations, void *scratch,
+                            int save_for_backward, float *out_loss, float *next_inv, float *next_off, void *stream) {
     int rc = check_rigid(P, F, k);
     if (rc) return rc;
     if (F == 0 || k == 0) return fail(GSR_ERR_ARG, "rigidity: no foreground edges (the mean is undefined)");
@@ -176,7 +183,46 @@ int gsr_rigidity_forward(int P, int F, int k, const float *means, const float *r
     HIP_TRY(launch_rigid_fwd(F, k, means, rotation_quaternions, foreground_rows, neighbor_rows, weights,
                              previous_offsets, previous_inverted_rotations, (double *)(base + L.partial),
                              sv ? (float *)(base + L.save_u) : nullptr, sv ? (float *)(base + L.save_m) : nullptr,
-                             sv ? (float *)(base + L.save_q) : nullptr, out_loss, s));
+                             sv ? (float *)(base + L.save_q) : nullptr, out_loss, next_inv, next_off, s));
+    return GSR_OK;
+}
+
+int gsr_rigidity_forward(int P, int F, int k, const float *means, const float *rotation_quaternions,
+                         const int *foreground_rows, const int *neighbor_rows, const float *weights,
+                         const float *previous_offsets, const float *previous_inverted_rotations, void *scratch,
+                         int save_for_backward, float *out_loss, void *stream) {
+    return rigidity_forward(P, F, k, means, rotation_quaternions, foreground_rows, neighbor_rows, weights,
+                            previous_offsets, previous_inverted_rotations, scratch, save_for_backward, out_loss, nullptr,
+                            nullptr, stream);
+}
+
+int gsr_rigidity_forward_state(int P, int F, int k, const float *means, const float *rotation_quaternions,
+                               const int *foreground_rows, const int *neighbor_rows, const float *weights,
+                               const float *previous_offsets, const float *previous_inverted_rotations, void *scratch,
+                               int save_for_backward, float *out_loss, float *next_inverted_rotations,
+                               float *next_offsets, void *stream) {
+    int rc = check_foreground(P, F, k);
+    if (rc) return rc;
+    if (!next_inverted_rotations || !next_offsets)
+        return fail(GSR_ERR_ARG, "rigidity: the state outputs are both required (gsr_rigidity_forward computes none)");
+    return rigidity_forward(P, F, k, means, rotation_quaternions, foreground_rows, neighbor_rows, weights,
+                            previous_offsets, previous_inverted_rotations, scratch, save_for_backward, out_loss,
+                            next_inverted_rotations, next_offsets, stream);
+}
+
+int gsr_foreground_info(int P, int F, int k, const float *means, const float *rotation_quaternions,
+                        const int *foreground_rows, const int *neighbor_rows, float *out_inverted_rotations,
+                        float *out_offsets, void *stream) {
+    int rc = check_foreground(P, F, k);
+    if (rc) return rc;
+    if (!foreground_rows || (out_inverted_rotations && !rotation_quaternions) ||
+        (out_offsets && (!means || !neighbor_rows)))
+        return fail(GSR_ERR_ARG, "foreground_info: null pointer");
+    if (!out_inverted_rotations && !out_offsets) return GSR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "foreground_info");
+    HIP_TRY(launch_foreground_info(F, k, means, rotation_quaternions, foreground_rows, neighbor_rows,
+                                   out_inverted_rotations, out_offsets, s));
     return GSR_OK;
 }
 

@@ -132,7 +132,9 @@ int rigid_blocks(int F);
 hipError_t launch_rigid_fwd(int F, int k, const float *means, const float *quats, const int *fg_rows,
                             const int *nbr_rows, const float *weights, const float *prev_off, const float *prev_inv,
                             double *partial, float *save_u, float *save_m, float *save_q, float *out_loss,
-                            hipStream_t s);
+                            float *next_inv, float *next_off, hipStream_t s);  // next_*: both or neither
+hipError_t launch_foreground_info(int F, int k, const float *means, const float *quats, const int *fg_rows,
+                                  const int *nbr_rows, float *out_inv, float *out_off, hipStream_t s);
 hipError_t launch_rigid_bwd(int P, int F, int k, const int *row_to_fg, const int *rev_off, const int *rev_edge,
                             const float *save_u, const float *save_m, const float *save_q, const float *g_loss,
                             float *dmeans, float *dquats, hipStream_t s);

@@ -20,6 +20,11 @@
 //                backward will follow it also stores d(sum of terms)/d(everything): per edge the
 //                world-space vector u_ij = d/dm_nbr, per Gaussian -sum_j u_ij and the gradient of its
 //                raw quaternion (through both normalisations).  Per-block double partial sums.
+//                A second instantiation also stores the state the NEXT timestep compares with, from
+//                the q and m_nbr - m_i it already holds.
+//   k_foreground_info  that state alone (create_foreground_info, train.py:228-248): one lane per
+//                foreground Gaussian, conj(q) as one float4 and the k offsets in the (k, 3, F) layout
+//                k_rigid_fwd reads.
 //   k_rigid_sum  one block: fixed-order sum of the block partials -> mean over the F k terms.
 //   k_rigid_bwd  one lane per row of the full (P, .) parameter arrays: a foreground row adds the stored
 //                u of the edges that list it (reverse adjacency, CSR, fixed order: no float atomics)
@@ -97,14 +102,53 @@ __device__ inline double block_sum_fixed(double v, double *s_w) {
     return t;
 }
 
+// The state the next timestep's rigidity term compares with (create_foreground_info, train.py:228-248),
+// from values a lane of foreground Gaussian i holds: the conjugate of its normalised quaternion, and
+// the offset to its j-th neighbour in the (k, 3, F) layout k_rigid_fwd reads as prev_off (lane-adjacent
+// stores).
+__device__ inline float4 inverted_rotation(float4 q) { return make_float4(q.x, -q.y, -q.z, -q.w); }
+__device__ inline void store_offset(float *__restrict__ out_off, int F, int j, int i, float d0, float d1, float d2) {
+    const size_t o = (3 * (size_t)j) * F + i;
+    out_off[o] = d0; out_off[o + F] = d1; out_off[o + 2 * (size_t)F] = d2;
+}
+
+// One lane per foreground Gaussian: the state alone, where no loss precedes it (a sequence's first
+// timestep, inference).  Either output may be NULL: it is then neither computed nor stored.  Only
+// foreground rows of means / quats are read.
+__global__ __launch_bounds__(kRigBlock) void k_foreground_info(int F, int k, const float *__restrict__ means,
+                                                               const float *__restrict__ quats,
+                                                               const int *__restrict__ fg_rows,
+                                                               const int *__restrict__ nbr_rows,
+                                                               float4 *__restrict__ out_inv, float *__restrict__ out_off) {
+    const int i = blockIdx.x * kRigBlock + threadIdx.x;
+    if (i >= F) return;
+    const size_t row = (size_t)fg_rows[i];
+    if (out_inv) {
+        const float4 raw = reinterpret_cast<const float4 *>(quats)[row];
+        out_inv[i] = inverted_rotation(act_normalize(raw, quat_norm(raw)));
+    }
+    if (out_off) {
+        const float mx = means[3 * row], my = means[3 * row + 1], mz = means[3 * row + 2];
+#pragma unroll 4
+        for (int j = 0; j < k; ++j) {
+            const size_t nr = (size_t)nbr_rows[(size_t)j * F + i];
+            store_offset(out_off, F, j, i, means[3 * nr] - mx, means[3 * nr + 1] - my, means[3 * nr + 2] - mz);
+        }
+    }
+}
+
 // save_* (all three or none): d(sum of the F k terms)/d(neighbour mean) per edge (k, F, 3), its negated
 // sum over a Gaussian's own edges (F, 3) and d/d(raw quaternion) (F, 4).
+// kState: also store this cloud's state (next_inv (F, 4), next_off (k, 3, F), both required) from the q
+// and d0..d2 the loss is evaluated with; the other instantiation holds none of that code.
+template <bool kState>
 __global__ __launch_bounds__(kRigBlock) void k_rigid_fwd(int F, int k, const float *__restrict__ means,
                                                          const float *__restrict__ quats, const int *__restrict__ fg_rows,
                                                          const int *__restrict__ nbr_rows, const float *__restrict__ weights,
                                                          const float *__restrict__ prev_off, const float4 *__restrict__ prev_inv,
                                                          double *__restrict__ partial, float *__restrict__ save_u,
-                                                         float *__restrict__ save_m, float4 *__restrict__ save_q) {
+                                                         float *__restrict__ save_m, float4 *__restrict__ save_q,
+                                                         float4 *__restrict__ next_inv, float *__restrict__ next_off) {
     __shared__ double s_w[kRigBlock / 64];
     const int i = blockIdx.x * kRigBlock + threadIdx.x;
     double sum = 0;
@@ -115,6 +159,7 @@ __global__ __launch_bounds__(kRigBlock) void k_rigid_fwd(int F, int k, const flo
         const float4 p = prev_inv[i];
         const float nraw = quat_norm(raw);
         const float4 q = act_normalize(raw, nraw);
+        if constexpr (kState) next_inv[i] = inverted_rotation(q);
         // quat_mult(q, p), train.py:311-318 (components (w, x, y, z) = (.x, .y, .z, .w))
         const float4 rel = make_float4(q.x * p.x - q.y * p.y - q.z * p.z - q.w * p.w,
                                        q.x * p.y + q.y * p.x + q.z * p.w - q.w * p.z,
@@ -135,6 +180,7 @@ __global__ __launch_bounds__(kRigBlock) void k_rigid_fwd(int F, int k, const flo
             const float ox = prev_off[(3 * (size_t)j) * F + i], oy = prev_off[(3 * (size_t)j + 1) * F + i],
                         oz = prev_off[(3 * (size_t)j + 2) * F + i];
             const float d0 = means[3 * nr] - mx, d1 = means[3 * nr + 1] - my, d2 = means[3 * nr + 2] - mz;
+            if constexpr (kState) store_offset(next_off, F, j, i, d0, d1, d2);
             const float e0 = (R00 * d0 + R10 * d1 + R20 * d2) - ox;
             const float e1 = (R01 * d0 + R11 * d1 + R21 * d2) - oy;
             const float e2 = (R02 * d0 + R12 * d1 + R22 * d2) - oz;
@@ -243,14 +289,26 @@ int rigid_blocks(int F) { return div_up(F, kRigBlock); }
 hipError_t launch_rigid_fwd(int F, int k, const float *means, const float *quats, const int *fg_rows,
                             const int *nbr_rows, const float *weights, const float *prev_off, const float *prev_inv,
                             double *partial, float *save_u, float *save_m, float *save_q, float *out_loss,
-                            hipStream_t s) {
+                            float *next_inv, float *next_off, hipStream_t s) {
     const int nb = rigid_blocks(F);
-    k_rigid_fwd<<<nb, kRigBlock, 0, s>>>(F, k, means, quats, fg_rows, nbr_rows, weights, prev_off,
-                                         reinterpret_cast<const float4 *>(prev_inv), partial, save_u, save_m,
-                                         reinterpret_cast<float4 *>(save_q));
+    const float4 *pinv = reinterpret_cast<const float4 *>(prev_inv);
+    float4 *sq = reinterpret_cast<float4 *>(save_q);
+    if (next_inv && next_off)
+        k_rigid_fwd<true><<<nb, kRigBlock, 0, s>>>(F, k, means, quats, fg_rows, nbr_rows, weights, prev_off, pinv, partial,
+                                                   save_u, save_m, sq, reinterpret_cast<float4 *>(next_inv), next_off);
+    else
+        k_rigid_fwd<false><<<nb, kRigBlock, 0, s>>>(F, k, means, quats, fg_rows, nbr_rows, weights, prev_off, pinv, partial,
+                                                    save_u, save_m, sq, nullptr, nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_rigid_sum<<<1, 256, 0, s>>>(nb, partial, 1.0 / ((double)F * k), out_loss);
+    return hipGetLastError();
+}
+
+hipError_t launch_foreground_info(int F, int k, const float *means, const float *quats, const int *fg_rows,
+                                  const int *nbr_rows, float *out_inv, float *out_off, hipStream_t s) {
+    k_foreground_info<<<rigid_blocks(F), kRigBlock, 0, s>>>(F, k, means, quats, fg_rows, nbr_rows,
+                                                            reinterpret_cast<float4 *>(out_inv), out_off);
     return hipGetLastError();
 }
 

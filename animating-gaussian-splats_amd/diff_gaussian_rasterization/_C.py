@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "gsr_posenc_ranges", "gsr_posenc_forward", "gsr_deform_in_forward", "gsr_deform_in_workspace_bytes",
     "gsr_deform_in_backward", "gsr_resblock_workspace_bytes", "gsr_resblock_forward", "gsr_resblock_backward",
     "gsr_deform_out_forward", "gsr_deform_out_workspace_bytes", "gsr_deform_out_backward",
+    "gsr_foreground_info", "gsr_rigidity_forward_state",
 )
 
 
@@ -230,6 +231,9 @@ def _optional():
             "gsr_deform_out_forward": (i, [i, i] + [vp] * 7),
             "gsr_deform_out_workspace_bytes": (sz, [i, i, i]),
             "gsr_deform_out_backward": (i, [i, i, vp, vp, vp, vp, i, vp, vp, vp, vp])}),
+        "foreground": ("the rigidity term's per-timestep state", {
+            "gsr_foreground_info": (i, [i, i, i] + [vp] * 7),
+            "gsr_rigidity_forward_state": (i, [i, i, i] + [vp] * 8 + [i] + [vp] * 4)}),
     }
 
 
@@ -240,8 +244,9 @@ _MISSING = {}  # feature -> why its entry points could not be bound (a stale lib
 
 
 def feature_library(name):
-    """The library, for the optional feature ``name`` of splat_deform ("deform", "resblock" or "head"): raises
-    when ``libgsr.so`` predates its entry points, on first use of the feature only."""
+    """The library, for the optional feature ``name``: "deform", "resblock" or "head" of splat_deform, or
+    "foreground" of splat_rigidity (``foreground_info``, ``calculate_rigidity_loss_and_state``).  Raises when
+    ``libgsr.so`` predates its entry points, on first use of the feature only."""
     L = load_library()
     if name in _MISSING:
         raise RuntimeError(f"libgsr.so at {LIB_PATH} lacks {_OPTIONAL[name][0]} ({_MISSING[name]}): "

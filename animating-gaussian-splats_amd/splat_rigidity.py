@@ -9,6 +9,16 @@ Drop-ins for the three rigidity call sites of the reference's ``train.py``:
   kernel and one backward kernel (csrc/gsr_rigidity.hip) instead of a dozen torch ops over
   ``(F, k, 3)`` intermediates and an autograd scatter.
 
+The state a timestep hands to the next one (what ``create_foreground_info`` restates with torch ops) also
+comes from the kernels, in one launch and without a host synchronisation:
+
+* ``foreground_info(params, neighbor_info)`` -- the state of a cloud on its own (a sequence's first
+  timestep, inference), from the packed neighbour lists;
+* ``calculate_rigidity_loss_and_state(params, neighbor_info, foreground_info)`` -- the loss and, as a side
+  output of its forward kernel, the state of the cloud it evaluated.
+
+Both return a ``ForegroundInfo`` whose ``(F, k, 3)`` offsets are a view of the kernels' ``(k, 3, F)`` buffer.
+
 ``knn`` is exact (brute force, float64 distances from the fp32 coordinates).  A point is excluded from
 its own list BY INDEX -- the reference drops "the first result" of a (k + 1)-query, which is the query
 point only when no other point coincides with it -- and equal distances are ordered by the lower
@@ -30,7 +40,8 @@ import torch
 from diff_gaussian_rasterization import _C
 
 __all__ = ["knn", "NeighborInfo", "ForegroundInfo", "PackedNeighbors", "pack_neighbors", "create_neighbor_info",
-           "create_foreground_info", "calculate_rigidity_loss"]
+           "create_foreground_info", "calculate_rigidity_loss", "foreground_info",
+           "calculate_rigidity_loss_and_state"]
 
 MAX_K = 32
 
@@ -222,10 +233,23 @@ def _packed_offsets(info, F, k):
     return packed
 
 
+def _empty_state(nb, dev):
+    """Uninitialised (inverted rotations (F, 4), offsets (k, 3, F)): the kernels write every element."""
+    return (torch.empty((nb.F, 4), dtype=torch.float32, device=dev),
+            torch.empty((nb.k, 3, nb.F), dtype=torch.float32, device=dev))
+
+
+def _state_info(inv, packed):
+    """ForegroundInfo over the kernels' two arrays: the reference-layout offsets are a view of ``packed``."""
+    return ForegroundInfo(inverted_rotations=inv, offsets_to_neighbors=packed.permute(2, 0, 1), packed_offsets=packed)
+
+
 class _Rigidity(torch.autograd.Function):
+    """``state``: also return the evaluated cloud's own (inverted rotations, packed offsets), non-differentiable."""
+
     @staticmethod
-    def forward(ctx, means, quats, nb, prev_off, prev_inv):
-        L = _C.load_library()
+    def forward(ctx, means, quats, nb, prev_off, prev_inv, state=False):
+        L = _C.feature_library("foreground") if state else _C.load_library()
         m, q = means.contiguous(), quats.contiguous()
         for t in (m, q, prev_off, prev_inv):
             _C._ptr(t)  # GPU + float32 checks (no CPU path)
@@ -233,21 +257,29 @@ class _Rigidity(torch.autograd.Function):
         save = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         scratch = torch.empty(L.gsr_rigidity_scratch_bytes(nb.F, nb.k, int(save)), dtype=torch.uint8, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
+        args = (nb.P, nb.F, nb.k, m.data_ptr(), q.data_ptr(), nb.foreground_rows.data_ptr(),
+                nb.neighbor_rows.data_ptr(), nb.weights.data_ptr(), prev_off.data_ptr(), prev_inv.data_ptr(),
+                scratch.data_ptr(), int(save), loss.data_ptr())
         with _C._device_guard(dev):
-            _C._check(L.gsr_rigidity_forward(nb.P, nb.F, nb.k, m.data_ptr(), q.data_ptr(),
-                                             nb.foreground_rows.data_ptr(), nb.neighbor_rows.data_ptr(),
-                                             nb.weights.data_ptr(), prev_off.data_ptr(), prev_inv.data_ptr(),
-                                             scratch.data_ptr(), int(save), loss.data_ptr(), _C._stream_ptr(dev)))
+            if state:
+                inv, off = _empty_state(nb, dev)
+                _C._check(L.gsr_rigidity_forward_state(*args, inv.data_ptr(), off.data_ptr(), _C._stream_ptr(dev)))
+            else:
+                _C._check(L.gsr_rigidity_forward(*args, _C._stream_ptr(dev)))
         if save:
             ctx.save_for_backward(scratch)
             ctx.nb = nb
         ctx.set_materialize_grads(False)
+        if state:
+            ctx.mark_non_differentiable(inv, off)
+            return loss, inv, off
         return loss
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, *_state_grads):
+        nothing = (None,) * (len(ctx.needs_input_grad) - 2)  # nb, the previous state, the flag
         if g is None:
-            return None, None, None, None, None
+            return (None, None) + nothing
         L = _C.load_library()
         (scratch,) = ctx.saved_tensors
         nb = ctx.nb
@@ -261,7 +293,7 @@ class _Rigidity(torch.autograd.Function):
                                               scratch.data_ptr(), g.data_ptr(),
                                               dm.data_ptr() if dm is not None else None,
                                               dq.data_ptr() if dq is not None else None, _C._stream_ptr(dev)))
-        return dm, dq, None, None, None
+        return (dm, dq) + nothing
 
 
 def calculate_rigidity_loss(params, neighbor_info, foreground_info):
@@ -279,3 +311,54 @@ def calculate_rigidity_loss(params, neighbor_info, foreground_info):
     prev_off = _packed_offsets(foreground_info, nb.F, nb.k)
     prev_inv = foreground_info.inverted_rotations.detach().float().contiguous()
     return _Rigidity.apply(means, quats, nb, prev_off, prev_inv)
+
+
+def _checked_cloud(params):
+    """(means (P, 3), rotation_quaternions (P, 4)) of ``params`` for the state calls: shapes and float32
+    are a ``ValueError``, a CPU tensor raises (no CPU path)."""
+    means, quats = params["means"], params["rotation_quaternions"]
+    P = means.shape[0]
+    if tuple(means.shape) != (P, 3) or tuple(quats.shape) != (P, 4):
+        raise ValueError(f"rigidity: means {tuple(means.shape)} / rotation_quaternions {tuple(quats.shape)}, "
+                         f"expected (P, 3) / (P, 4)")
+    if means.dtype != torch.float32 or quats.dtype != torch.float32:
+        raise ValueError(f"rigidity: means {means.dtype} / rotation_quaternions {quats.dtype}, expected float32")
+    _need_gpu(means, "params")
+    _need_gpu(quats, "params")
+    return means, quats
+
+
+def foreground_info(params, neighbor_info):
+    """``create_foreground_info`` (train.py:228-248) of the cloud ``params`` in one kernel launch, from the
+    packed neighbour lists: no torch op over (F, .) data and no host synchronisation (a bare object with
+    only ``indices`` / ``weights`` is packed and validated once, as in ``calculate_rigidity_loss``).  The
+    inputs are detached.  The offsets are written once, in the kernels' (k, 3, F) layout
+    (``packed_offsets``); ``offsets_to_neighbors`` (F, k, 3) is a view of that buffer."""
+    means, quats = _checked_cloud(params)
+    nb = _packed_neighbors(params, neighbor_info)
+    if nb.k > MAX_K:
+        raise ValueError(f"foreground_info: k must be in [1, {MAX_K}], got {nb.k}")
+    L = _C.feature_library("foreground")
+    m, q = means.detach().contiguous(), quats.detach().contiguous()
+    dev = m.device
+    inv, off = _empty_state(nb, dev)
+    with _C._device_guard(dev):
+        _C._check(L.gsr_foreground_info(nb.P, nb.F, nb.k, m.data_ptr(), q.data_ptr(), nb.foreground_rows.data_ptr(),
+                                        nb.neighbor_rows.data_ptr(), inv.data_ptr(), off.data_ptr(),
+                                        _C._stream_ptr(dev)))
+    return _state_info(inv, off)
+
+
+def calculate_rigidity_loss_and_state(params, neighbor_info, foreground_info):
+    """``(calculate_rigidity_loss(params, neighbor_info, foreground_info), foreground_info(params,
+    neighbor_info))`` from one forward kernel: the state of the evaluated cloud is stored from the values
+    the loss is computed with.  The loss carries the same gradients as ``calculate_rigidity_loss``'s; the
+    state is not differentiable."""
+    means, quats = _checked_cloud(params)
+    nb = _packed_neighbors(params, neighbor_info)
+    if nb.k > MAX_K:
+        raise ValueError(f"calculate_rigidity_loss_and_state: k must be in [1, {MAX_K}], got {nb.k}")
+    prev_off = _packed_offsets(foreground_info, nb.F, nb.k)
+    prev_inv = foreground_info.inverted_rotations.detach().float().contiguous()
+    loss, inv, off = _Rigidity.apply(means, quats, nb, prev_off, prev_inv, True)
+    return loss, _state_info(inv, off)

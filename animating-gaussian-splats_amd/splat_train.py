@@ -17,6 +17,7 @@ optimizer.step(); zero_grad(set_to_none)    :246-247    splat_adam.FusedAdam (on
 
 ``train_step_loss`` is the loss of one train.py step (train.py:395-418): the views' renders and image
 losses as above plus the rigidity term of ``splat_rigidity``, evaluated once per step.
+``advance_timestep`` hands a finished timestep's cloud and rigidity state to the next (train.py:251-266).
 
 ``View`` restates shared.py:13-18.  The image-render ``means2D`` is a leaf that receives the same
 screen-space (NDC) gradient the reference reads through ``retain_grad`` (densify.py:119).
@@ -32,7 +33,7 @@ import splat_loss
 import splat_rigidity
 from diff_gaussian_rasterization import GaussianRasterizationSettings, rasterize_parameters
 
-__all__ = ["View", "densify_iteration", "create_densification_variables", "train_step_loss"]
+__all__ = ["View", "densify_iteration", "create_densification_variables", "train_step_loss", "advance_timestep"]
 
 
 @dataclass
@@ -76,12 +77,17 @@ def densify_iteration(params, view, densification_variables, optimizer, scene_ra
     return (total.detach(), image_loss.detach(), segmentation_loss.detach()), info
 
 
-def train_step_loss(params, views, neighbor_info, foreground_info):
+def train_step_loss(params, views, neighbor_info, foreground_info, next_foreground_info=False):
     """train.py:395-418 ``calculate_loss`` without the logging: every view rendered
     (``rasterize_parameters``) and compared (fused L1 + SSIM), plus the rigidity term.  The reference
     evaluates the rigidity term once per view although it does not depend on the view; here it is
     evaluated once and multiplied by ``V = len(views)``.  Returns ``(0.8 sum l1 + 0.2 sum (1 - ssim) +
-    3 V rigidity, sum l1, sum (1 - ssim), V rigidity)``; call ``backward()`` on the first."""
+    3 V rigidity, sum l1, sum (1 - ssim), V rigidity)``; call ``backward()`` on the first.
+
+    ``next_foreground_info``: a fifth element, the ``ForegroundInfo`` of ``params`` -- what the next
+    timestep's rigidity term compares with (train.py:759-765 builds it after the loss) -- stored by the
+    rigidity forward kernel itself (``calculate_rigidity_loss_and_state``; DESIGN.md 6 has the timing
+    against a separate ``splat_rigidity.foreground_info`` launch)."""
     if not views:
         raise ValueError("train_step_loss: no views")
     l1_sum = ssim_sum = None
@@ -90,6 +96,25 @@ def train_step_loss(params, views, neighbor_info, foreground_info):
         l1, ssim_loss = splat_loss.l1_and_ssim_loss(image, view.image)
         l1_sum = l1 if l1_sum is None else l1_sum + l1
         ssim_sum = ssim_loss if ssim_sum is None else ssim_sum + ssim_loss
-    rigidity_sum = len(views) * splat_rigidity.calculate_rigidity_loss(params, neighbor_info, foreground_info)
+    if next_foreground_info:
+        rigidity, state = splat_rigidity.calculate_rigidity_loss_and_state(params, neighbor_info, foreground_info)
+    else:
+        rigidity = splat_rigidity.calculate_rigidity_loss(params, neighbor_info, foreground_info)
+    rigidity_sum = len(views) * rigidity
     total = 0.8 * l1_sum + 0.2 * ssim_sum + 3 * rigidity_sum
+    if next_foreground_info:
+        return total, l1_sum, ssim_sum, rigidity_sum, state
     return total, l1_sum, ssim_sum, rigidity_sum
+
+
+def advance_timestep(updated_params, neighbor_info, foreground_info=None):
+    """train.py:251-266 ``compute_encoded_normalized_means_and_rotations_and_foreground_info`` between two
+    timesteps: ``(previous_params, ForegroundInfo)`` for the next one.  ``previous_params`` is every entry
+    of ``updated_params`` detached; nothing is encoded here, ``splat_deform.deform_input_layer`` takes the
+    dict.  The state is ``foreground_info`` when given (the one ``train_step_loss(...,
+    next_foreground_info=True)`` returned for the same cloud), else ``splat_rigidity.foreground_info`` of
+    the updated cloud: one launch, no host synchronisation."""
+    previous_params = {name: value.detach() for name, value in updated_params.items()}
+    if foreground_info is None:
+        foreground_info = splat_rigidity.foreground_info(previous_params, neighbor_info)
+    return previous_params, foreground_info

@@ -400,6 +400,24 @@ int gsr_rigidity_forward(int P, int F, int k, const float *means, const float *r
 int gsr_rigidity_backward(int P, int F, int k, const int *row_to_foreground, const int *reverse_offsets,
                           const int *reverse_edges, const void *scratch, const float *dL_dloss, float *dL_dmeans,
                           float *dL_drotation_quaternions, void *stream);
+/* The state the NEXT timestep's rigidity term compares with (create_foreground_info, train.py:228-248),
+ * additive to ABI 21.  out_inverted_rotations (F, 4): the normalised quaternion (q / max(|q|, 1e-12)) of
+ * each foreground row with x, y, z negated; out_offsets (k, 3, F): means[neighbor_rows[j F + i]] - mean_i,
+ * the layout gsr_rigidity_forward takes as previous_offsets.  Inputs as for gsr_rigidity_forward; only
+ * foreground rows of means / rotation_quaternions are read.  Either output may be NULL: it is then not
+ * computed.  One launch, no host synchronisation.  F > 0, 1 <= k <= 32, F <= P, else an error and no launch. */
+int gsr_foreground_info(int P, int F, int k, const float *means, const float *rotation_quaternions,
+                        const int *foreground_rows, const int *neighbor_rows, float *out_inverted_rotations,
+                        float *out_offsets, void *stream);
+/* gsr_rigidity_forward that also stores the state of the cloud it evaluates, bit for bit what
+ * gsr_foreground_info gives, from the values the loss is computed with.  Both state outputs are required
+ * and must not overlap the previous state; the loss and the saved derivatives are those of
+ * gsr_rigidity_forward.  The same size limits as gsr_foreground_info. */
+int gsr_rigidity_forward_state(int P, int F, int k, const float *means, const float *rotation_quaternions,
+                               const int *foreground_rows, const int *neighbor_rows, const float *weights,
+                               const float *previous_offsets, const float *previous_inverted_rotations, void *scratch,
+                               int save_for_backward, float *out_loss, float *next_inverted_rotations,
+                               float *next_offsets, void *stream);
 
 /* ---- Deformation network input layer (additive to ABI 21) --------------------------------------
  * The encoded input of train.py's DeformationNetwork and its first linear layer.  An encoding takes
@@ -581,7 +599,7 @@ int gsr_views_pack(int frames, int H, int W, const uint8_t *rgb, const uint8_t *
 
 /* Per-phase device timing with HIP events recorded on the call's stream (off by default).
  * Phases: "preprocess", "bin_count", "bin_scan", "bin_emit", "tile_sort", "render_fwd",
- * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "knn", "rigidity_fwd", "rigidity_bwd",
+ * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "knn", "rigidity_fwd", "rigidity_bwd", "foreground_info",
  * "posenc_ranges", "posenc", "deform_in_fwd", "deform_in_bwd", "resblock_fwd", "resblock_bwd", "deform_out_fwd", "deform_out_bwd".  gsr_profile_read synchronises on the recorded events. */
 int gsr_profile_enable(int on);
 /* Restrict event recording to a comma-separated list of phases (NULL or "" = every phase), so a
