@@ -9,13 +9,18 @@
 //   k_ssim_fwd   one wave64 per 64-column x 32-row strip of one image plane, 4 independent waves per
 //                block: rows stream through wave-private LDS (11-tap horizontal pass of
 //                (x, y, x^2, y^2, xy)) into an 11-row register ring (vertical pass), then per pixel
-//                the SSIM value, its three partial derivatives dS/dmu1, dS/d<x^2>, dS/d<xy> (stored
+//                the SSIM value, three derivative maps dS/dmu1, dS/d<x^2>, dS/d<xy> + 2 dS/d<x^2> (stored
 //                for the backward) and |x - y|.  Per-wave partial sums, no atomics.
 //   k_ssim_sum   one block: fixed-order (double) sum of the block partials -> (mean |x-y|, mean S).
 //   k_ssim_bwd   same strips: blur the three stored derivative maps (the window is symmetric, so the
 //                adjoint of the zero-padded correlation is the same correlation) and combine
 //                dL/dx = gS/N (blur(dS/dmu1) + 2 x blur(dS/d<x^2>) + y blur(dS/d<xy>)) + gL1/N sign(x-y)
 //                with the upstream gradients gL1, gS read from device memory (no host sync).
+//                dS/d<x^2> = -S / D and dS/d<xy> = 2 A / (C D) are each ~ 1 / c2 = 1111 on a flat region and
+//                cancel to ~ 0 where the render matches its target, so their fp32 roundings (7e-5 each)
+//                would be the whole result there.  The third map therefore holds the sum
+//                dS/d<xy> + 2 dS/d<x^2> = 2 (A - S C) / (C D), cancelled before it is rounded, and the
+//                backward combines 2 (x - y) blur(dS/d<x^2>) + y blur(third map): the same gradient.
 //
 // Algorithmic HBM bytes: forward 2 reads + 3 writes per pixel (20 B), backward 3 + 2 reads + 1
 // write (24 B); the 10 halo rows per 32-row strip and the 10 halo columns re-read through L2.
@@ -128,11 +133,13 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int planes, int H, int W, int 
                     const float S = (A * B) * inv;
                     ssum += S;
                     // S = A B / (C D): dS/dmu1 = (2 mu2 (B - A) - 2 mu1 S (D - C)) / (C D),
-                    // dS/d<x^2> = -S / D, dS/d<xy> = 2 A / (C D)
+                    // dS/d<x^2> = -S / D, dS/d<xy> = 2 A / (C D); the third map is dS/d<xy> + 2 dS/d<x^2>
                     const size_t p = (size_t)gy * W + gx;
-                    m0[p] = (2.f * mu2 * (B - A) - 2.f * mu1 * S * (D - C)) * inv;
+                    // S multiplies one rounded product, not 2 mu1 first: where mu1 = mu2, A = C and B = D the two
+                    // terms are then the same float and their difference is (1 - S) of it, not a rounding of 2 mu1 S
+                    m0[p] = 2.f * fmaf(-S, mu1 * (D - C), mu2 * (B - A)) * inv;
                     m0[map_stride + p] = -S / D;
-                    m0[2 * map_stride + p] = 2.f * A * inv;
+                    m0[2 * map_stride + p] = 2.f * fmaf(-S, C, A) * inv;
                 }
             }
         }
@@ -235,7 +242,7 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(int planes, int H, int W, int 
                     const float x = a[p], y = b[p];
                     const float dd = x - y;
                     const float sgn = dd > 0.f ? 1.f : (dd < 0.f ? -1.f : 0.f);
-                    dst[p] = gs * (acc[0] + 2.f * x * acc[1] + y * acc[2]) + gl * sgn;
+                    dst[p] = gs * (acc[0] + 2.f * dd * acc[1] + y * acc[2]) + gl * sgn;
                 }
             }
         }

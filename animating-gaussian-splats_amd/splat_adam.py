@@ -5,8 +5,10 @@ per parameter, ``lr=0.0`` default, ``eps=1e-15``): same constructor arguments, `
 per-parameter ``state`` (``step`` CPU scalar tensor, ``exp_avg``, ``exp_avg_sq``), so the reference's
 optimizer surgery (external.py:127-204) and ``splat_densify`` work on it unchanged.  ``step()``
 updates every parameter with a gradient in ONE kernel launch, with torch's ``_multi_tensor_adam``
-operation order (parity within a few ulp; tests/test_adam.py).  Supported configuration: the
-reference's -- no weight decay, no AMSGrad, not maximising.  There is no CPU path.
+operation order: parameters, both moments and ``step`` are bitwise those of ``torch.optim.Adam`` on the
+same device (tests/test_adam.py), also for gradients that are exactly zero, whose square underflows or is
+subnormal (1e-30, 1e-22), or huge (1e18): no gradient class needs an ulp allowance.  Supported
+configuration: the reference's -- no weight decay, no AMSGrad, not maximising.  There is no CPU path.
 """
 from __future__ import annotations
 

@@ -5,6 +5,9 @@ CPU: the restatements of tests/deform_ref.py reproduce what the reference itself
 reference's state_dict and refuses CPU tensors and bad shapes.  GPU: the HIP kernels against the float64
 restatement.  "Project band": |got - ref| <= 1e-4 |ref| + 1e-6 max|ref| with no value outside (the band of
 tests/test_rigidity.py); "golden band": 2e-4 |ref| + 2e-5 max|ref| for values the reference saved in fp32.
+
+k_posenc_ranges runs at most 256 workgroups of 256 rows and strides over the rest, so rows >= 65,536 are a
+second trip of its loop: the P = 65,836 cases put every column's minimum and maximum (and, once, a NaN) there.
 """
 import functools
 import os
@@ -192,6 +195,119 @@ def test_encode_means_and_rotations(cuda, P, constant):
     err = float((got.double() - r64)[ok].abs().max())
     print(f"P={P} constant={constant}: kernel {err:.3e}, float32 torch restatement {yard:.3e}")
     assert err <= max(2 * yard, ULP2)
+
+
+# ---- the range kernel's second trip (P > 65,536) ----------------------------------------------------
+RANGE_TRIP = 256 * 256  # GSR_POSENC_RANGE_BLOCKS workgroups x 256 rows
+P_LATE = RANGE_TRIP + 300
+
+
+@functools.lru_cache(maxsize=None)
+def _late_clouds():
+    """The seeded clouds at P_LATE rows with every column's minimum and maximum moved into rows >= 65,536
+    (a different row for each of the 28 extremes)."""
+    clouds = tuple({k: v.clone() for k, v in c.items()} for c in _clouds(P_LATE))
+    row = RANGE_TRIP + 3
+    for cloud in clouds:
+        for t in cloud.values():
+            for c in range(t.shape[1]):
+                lo, hi = float(t[:, c].min()), float(t[:, c].max())
+                t[row, c], t[row + 1, c] = lo - 0.37, hi + 0.61
+                row += 7
+    assert row < P_LATE
+    return clouds
+
+
+def _numpy_ranges(means, quats, rows=None):
+    """lo = min, hi = fp32(max - lo) per column, numpy fp32; ``rows``: the mistake restated, later rows ignored."""
+    x = np.concatenate((means.numpy(), quats.numpy()), axis=1)[:rows]
+    lo = x.min(axis=0)
+    return np.concatenate((lo, (x.max(axis=0) - lo).astype(np.float32)))
+
+
+def _sample_rows():
+    return torch.cat((torch.arange(0, 128), torch.arange(RANGE_TRIP - 128, P_LATE)))
+
+
+def test_late_extremes_and_range_sensitivity():
+    """Every extreme sits past the first trip; ranges from the first 65,536 rows alone differ in every one of the 14
+    values' bits, and the encoding they give moves by more than 100 of the GPU test's tolerances."""
+    for cloud in _late_clouds():
+        means, quats = cloud["means"], cloud["rotation_quaternions"]
+        x = torch.cat((means, quats), dim=1)
+        assert int(x.argmin(dim=0).min()) >= RANGE_TRIP and int(x.argmax(dim=0).min()) >= RANGE_TRIP
+        right, wrong = _numpy_ranges(means, quats), _numpy_ranges(means, quats, RANGE_TRIP)
+        assert (right.view(np.int32) != wrong.view(np.int32)).all()
+        rows = _sample_rows()
+        r32 = DR.encode_means_and_rotations(means, quats, torch.float32)[rows]
+        r64 = DR.encode_means_and_rotations(means, quats, torch.float64)[rows]
+        lo, hi = torch.from_numpy(wrong[:7]), torch.from_numpy(wrong[7:])
+        xn = (2.0 * (x - lo) / hi) - 1.0
+        moved = torch.cat((DR.encode_arguments(DR.arguments(xn[:, :3], 10)), DR.encode_arguments(DR.arguments(xn[:, 3:], 4))),
+                          dim=1)[rows]
+        tol = max(2 * float((r32.double() - r64).abs().max()), ULP2)
+        ratio = float((moved.double() - r64).abs().max()) / tol
+        print(f"ranges of the first trip only: the encoding moves by {ratio:.0f} tolerances")
+        assert ratio > 100
+
+
+@pytest.mark.gpu
+def test_encoding_ranges_second_trip(cuda):
+    for cloud in _late_clouds():
+        means, quats = cloud["means"], cloud["rotation_quaternions"]
+        got = D.encoding_ranges(means.to(cuda), quats.to(cuda)).cpu().numpy()
+        np.testing.assert_array_equal(got.view(np.int32), _numpy_ranges(means, quats).view(np.int32))
+
+
+@pytest.mark.gpu
+def test_encoding_ranges_keep_a_late_nan(cuda):
+    """A NaN in row 65,736 of the quaternion y column: its minimum and its range are NaN, as torch's reductions
+    (and numpy's) give; the other 12 values are untouched."""
+    cloud = {k: v.clone() for k, v in _late_clouds()[0].items()}
+    cloud["rotation_quaternions"][RANGE_TRIP + 200, 2] = float("nan")
+    means, quats = cloud["means"], cloud["rotation_quaternions"]
+    got = D.encoding_ranges(means.to(cuda), quats.to(cuda)).cpu().numpy()
+    ref = _numpy_ranges(means, quats)
+    col = 3 + 2
+    assert np.isnan(ref[[col, 7 + col]]).all() and np.isnan(ref).sum() == 2
+    assert torch.isnan(torch.cat((means, quats), dim=1).min(dim=0).values[col])
+    assert np.isnan(got[[col, 7 + col]]).all()
+    keep = ~np.isnan(ref)
+    np.testing.assert_array_equal(got[keep].view(np.int32), ref[keep].view(np.int32))
+
+
+@pytest.mark.gpu
+def test_encode_second_trip(cuda):
+    """test_encode_means_and_rotations' check on rows from both sides of row 65,536."""
+    cloud = _to(_late_clouds()[0], cuda)
+    got = D.encode_means_and_rotations(cloud)
+    assert got.shape == (P_LATE, 92)
+    rows = _sample_rows().to(cuda)
+    r32 = DR.encode_means_and_rotations(cloud["means"], cloud["rotation_quaternions"], torch.float32)[rows]
+    r64 = DR.encode_means_and_rotations(cloud["means"], cloud["rotation_quaternions"], torch.float64)[rows]
+    assert not torch.isnan(r64).any() and torch.isfinite(got).all()
+    yard = float((r32.double() - r64).abs().max())
+    err = float((got[rows].double() - r64).abs().max())
+    print(f"P={P_LATE}: kernel {err:.3e}, float32 torch restatement {yard:.3e}")
+    assert err <= max(2 * yard, ULP2)
+
+
+@pytest.mark.gpu
+def test_fused_layer_second_trip(cuda):
+    """deform_input_layer at H = 7 over P = 65,836 rows, with test_fused_forward's and test_fused_backward's checks."""
+    P, H = P_LATE, 7
+    initial, previous = (_to(c, cuda) for c in _late_clouds())
+    w, b, up = (t.to(cuda) for t in _layer(P, H))
+    x64 = DR.input_matrix(initial, previous, PROGRESS, torch.float64)
+    w, b = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    out = D.deform_input_layer(w, b, initial, previous, PROGRESS)
+    assert out.shape == (P, H) and out.dtype == torch.float32
+    band(f"fc_in output ({P}, {H})", out, x64 @ w.detach().double().t() + b.detach().double())
+    out.backward(up)
+    band(f"dW ({P}, {H})", w.grad, up.double().t() @ x64)
+    band(f"db ({P}, {H})", b.grad, up.double().sum(0))
+    pe64 = DR.encode_progress(PROGRESS, 1, cuda, torch.float64)[0]
+    band("dW[:, 184:] = enc(progress) db", w.grad[:, 184:], b.grad.double()[:, None] * pe64[None, :])
 
 
 # ---- GPU: the fused input layer -------------------------------------------------------------------

@@ -6,7 +6,13 @@ brute-force k-nearest-neighbour search) reproduce what the reference itself comp
 refuses CPU tensors.  GPU: the HIP kernels against those checkers and against the reference's saved
 values.  Gradient band everywhere but the golden comparisons: |got - ref| <= 1e-4 |ref| + 1e-6 max|ref|
 with no value outside (the reference's own fp32 run stays inside it, at most 8.4e-7 max|ref| off its
-float64 run at these perturbations)."""
+float64 run at these perturbations).
+
+Shapes chosen for the paths they reach: k_rigid_sum strides 256 threads over the per-block partials, so a second
+trip needs more than 256 partials, F > 65,536 (test_sum_second_trip: F = 65,836); k_knn<32> serves every
+k != 20 and is run at k = 1, 21 and 32 = K, and at n = 256 / 257 (one full candidate tile, then a tile and a
+query block with one live lane).  NOT covered: the query split of launch_knn -- its second launch (q0 > 0)
+needs n^2 > 2^37 pairs, n > 370,727 points: a full-size run of minutes, not a test."""
 import functools
 import os
 from types import SimpleNamespace
@@ -95,23 +101,57 @@ def test_no_cpu_path():
 
 
 # ---- GPU: neighbour search ------------------------------------------------------------------------
-@pytest.mark.gpu
-@pytest.mark.parametrize("n,k", [(4, 3), (21, 20), (64, 20), (65, 20), (300, 20), (4099, 20)])
-def test_knn_matches_brute_force(cuda, n, k):
-    g = torch.Generator().manual_seed(100 + n)
-    pts = torch.rand(n, 3, generator=g)
-    idx, d2 = R.knn(pts.to(cuda), k)
-    assert idx.dtype == torch.int64 and d2.dtype == torch.float64 and idx.shape == d2.shape == (n, k)
-    idx, d2 = idx.cpu().numpy(), d2.cpu().numpy()
+KNN_SHAPES = [(4, 3), (21, 20), (64, 20), (65, 20), (300, 20), (4099, 20),
+              (2, 1), (22, 21), (33, 32), (256, 32), (257, 32), (257, 21)]
+
+
+def _knn_points(n):
+    return torch.rand(n, 3, generator=torch.Generator().manual_seed(100 + n))
+
+
+def _knn_reference(pts, n, k):
+    """Brute-force (indices, distances) with one distance more than k where it exists, and the positions whose
+    distance is separated from both sorted neighbours by more than 1e-9 relative."""
     kk = min(k + 1, n - 1)  # the (k + 1)-th distance bounds the last position (absent when n = k + 1)
     ridx, rd2 = RR.brute_force_knn(pts.numpy(), kk)
-    assert (np.diff(d2, axis=1) >= 0).all()
-    assert (np.abs(d2 - rd2[:, :k]) <= 1e-12 * rd2[:, :k]).all()
-    assert (idx != np.arange(n)[:, None]).all()
-    # positions whose distance is separated from both sorted neighbours by more than 1e-9 relative
     ext = np.concatenate([np.full((n, 1), -np.inf), rd2, np.full((n, k + 2 - rd2.shape[1] - 1), np.inf)], axis=1)
     lo, mid, hi = ext[:, :k], ext[:, 1:k + 1], ext[:, 2:k + 2]
     clear = (mid - lo > 1e-9 * mid) & (hi - mid > 1e-9 * mid)
+    return ridx, rd2, clear
+
+
+@pytest.mark.parametrize("n,k", KNN_SHAPES)
+def test_knn_seeds_stay_under_the_near_tie_cap(n, k):
+    """The brute-force reference alone: the seeded points leave at most 1e-3 of the positions to the near-tie
+    exclusion, so the GPU test's index comparison covers the rest."""
+    ridx, rd2, clear = _knn_reference(_knn_points(n), n, k)
+    assert clear.shape == (n, k) and (~clear).mean() <= 1e-3
+    assert (ridx != np.arange(n)[:, None]).all() and (np.diff(rd2, axis=1) >= 0).all()
+
+
+@pytest.mark.parametrize("n,k", [(257, 32), (257, 21), (300, 20)])
+def test_knn_reference_is_sensitive_to_the_second_candidate_tile(n, k):
+    """The brute-force search with the candidates past the first tile of 256 left out: the point(s) of the
+    second tile are among somebody's k nearest, so index lists change at positions the GPU test compares."""
+    pts = _knn_points(n)
+    ridx, _, clear = _knn_reference(pts, n, k)
+    first_tile, _ = RR.brute_force_knn(pts.numpy()[:256], k)
+    changed = first_tile != ridx[:256, :k]
+    print(f"n={n} k={k}: {changed.sum()} compared positions change without the second candidate tile")
+    assert (changed & clear[:256]).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,k", KNN_SHAPES)
+def test_knn_matches_brute_force(cuda, n, k):
+    pts = _knn_points(n)
+    idx, d2 = R.knn(pts.to(cuda), k)
+    assert idx.dtype == torch.int64 and d2.dtype == torch.float64 and idx.shape == d2.shape == (n, k)
+    idx, d2 = idx.cpu().numpy(), d2.cpu().numpy()
+    ridx, rd2, clear = _knn_reference(pts, n, k)
+    assert (np.diff(d2, axis=1) >= 0).all()
+    assert (np.abs(d2 - rd2[:, :k]) <= 1e-12 * rd2[:, :k]).all()
+    assert (idx != np.arange(n)[:, None]).all()
     print(f"n={n}: {(~clear).sum()}/{clear.size} positions excluded as near-ties")
     assert (~clear).mean() <= 1e-3
     assert np.array_equal(idx[clear], ridx[:, :k][clear])
@@ -256,6 +296,52 @@ def test_uneven_reverse_adjacency(cuda, pert):
     packed = R.pack_neighbors(pg, ni.indices, ni.weights)
     counts = np.diff(packed.reverse_offsets.cpu().numpy())
     assert counts[0] == F - 1 and counts[F - 1] == 0 and counts.sum() == F * k
+    _check_parity(_perturbed(prev, g, *PERTURBATIONS[pert]), ni, fi, cuda)
+
+
+SUM_TRIP = 256 * 256  # k_rigid_sum: 256 threads over the partials of 256-row blocks
+
+
+def _second_trip_cloud():
+    """F = 65,536 + 300 foreground rows (258 block partials) after 30 background rows, k = 3, the neighbour lists
+    of test_uneven_reverse_adjacency: every Gaussian lists row 0, nobody lists the last one."""
+    F, k, B = SUM_TRIP + 300, 3, 30
+    mask = torch.arange(F + B) >= B
+    prev, g = _cloud(F + B, mask, seed=78)
+    i, j = torch.arange(F)[:, None], torch.arange(k)[None]
+    idx = 1 + (i + j) % (F - 2)
+    idx[:, 0] = 0
+    idx[0, 0] = 1
+    return F, k, mask, prev, g, idx, torch.rand(F, k, generator=g)
+
+
+@pytest.mark.parametrize("pert", [0, 1])
+def test_reference_is_sensitive_to_the_sum_second_trip(pert):
+    """The float64 restatement with the partials past the first 256 left out of the sum (the first 65,536 rows'
+    terms over the same F k): the loss moves by more than 100 of the GPU test's 1e-5 tolerances."""
+    F, k, mask, prev, g, idx, w = _second_trip_cloud()
+    inv, off = RR.foreground_info(prev["means"], prev["rotation_quaternions"], mask, idx, dtype=torch.float32)
+    cur = _perturbed(prev, g, *PERTURBATIONS[pert])
+    fm, fq = cur["means"].double()[mask], RR.unit(cur["rotation_quaternions"].double())[mask]
+    rot = RR.rotation_matrices(RR.hamilton(fq, inv.double()))
+    v = torch.einsum("frc,fkr->fkc", rot, fm[idx] - fm[:, None])
+    terms = ((v - off.double()).pow(2).sum(-1) * w.double() + 1e-20).sqrt()
+    full = RR.rigidity_loss(cur["means"], cur["rotation_quaternions"], mask, idx, w, inv, off)
+    assert abs(float(terms.mean()) - float(full)) <= 1e-12 * float(full)
+    first_trip = float(terms[:SUM_TRIP].sum()) / (F * k)
+    moved = abs(first_trip - float(full)) / (1e-5 * float(full))
+    print(f"first trip only: the loss moves by {moved:.0f} tolerances")
+    assert moved > 100
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pert", [0, 1])
+def test_sum_second_trip(cuda, pert):
+    F, k, mask, prev, g, idx, w = _second_trip_cloud()
+    ni = SimpleNamespace(indices=idx.to(cuda), weights=w.to(cuda))
+    pg = {n: v.to(cuda) for n, v in prev.items()}
+    fi = R.create_foreground_info(pg, ni.indices)
+    assert R.pack_neighbors(pg, ni.indices, ni.weights).F == F > SUM_TRIP
     _check_parity(_perturbed(prev, g, *PERTURBATIONS[pert]), ni, fi, cuda)
 
 
