@@ -623,21 +623,30 @@ __device__ inline void sh_basis16(float x, float y, float z, float (&basis)[16])
     basis[15] = kSH_C3[6] * x * (xx - 3.f * yy);
 }
 
+// What every SH chain of a view starts from: the view direction d0 = mean - campos, its unit vector
+// (x, y, z), and dL/dRGB = the colour gradient g with the channels the forward clamped at 0 (bit c of
+// the view's clamp mask, clamp_bits) zeroed.
+struct ShDir { float3 d0; float x, y, z, dRGB[3]; };
+__device__ inline ShDir sh_dir(float3 mean, float3 campos, uint32_t clampm, float g0, float g1, float g2) {
+    bool cl[3];
+    clamp_from_mask(clampm, cl);
+    ShDir s;
+    s.d0 = make_float3(mean.x - campos.x, mean.y - campos.y, mean.z - campos.z);
+    const float len = sqrtf(s.d0.x * s.d0.x + s.d0.y * s.d0.y + s.d0.z * s.d0.z);
+    s.x = s.d0.x / len; s.y = s.d0.y / len; s.z = s.d0.z / len;
+    s.dRGB[0] = g0 * (cl[0] ? 0.f : 1.f); s.dRGB[1] = g1 * (cl[1] ? 0.f : 1.f); s.dRGB[2] = g2 * (cl[2] ? 0.f : 1.f);
+    return s;
+}
+
 // The SH colour's derivative with respect to the mean (returned) and the coefficient gradients
 // (written to all M rows of dL_dsh, zeros past the active degree).  `sh` and `dL_dsh` may alias (the
 // same LDS row): phase 1 reads the coefficients (direction derivative), phase 2 writes the
 // coefficient gradients, which depend only on the direction and dL/dRGB.
 template <typename ShPtr, typename OutPtr>
-__device__ inline float3 sh_backward(int deg, int M, float3 mean, float3 campos, ShPtr sh,
-                                     const bool *clamped, float3 dL_dcolor, OutPtr dL_dsh, bool acc = false) {
-    const float3 d0 = make_float3(mean.x - campos.x, mean.y - campos.y, mean.z - campos.z);
-    const float len = sqrtf(d0.x * d0.x + d0.y * d0.y + d0.z * d0.z);
-    const float x = d0.x / len, y = d0.y / len, z = d0.z / len;
-    const float dRGB[3] = {dL_dcolor.x * (clamped[0] ? 0.f : 1.f), dL_dcolor.y * (clamped[1] ? 0.f : 1.f),
-                           dL_dcolor.z * (clamped[2] ? 0.f : 1.f)};
-    const float3 dL_ddir = sh_dir_grad(deg, x, y, z, sh, dRGB);
+__device__ inline float3 sh_backward(int deg, int M, const ShDir &sd, ShPtr sh, OutPtr dL_dsh, bool acc = false) {
+    const float3 dL_ddir = sh_dir_grad(deg, sd.x, sd.y, sd.z, sh, sd.dRGB);
     float basis[16];
-    sh_basis16(x, y, z, basis);
+    sh_basis16(sd.x, sd.y, sd.z, basis);
     const int active = (deg + 1) * (deg + 1);
     if (dL_dsh) {  // null: the coefficients' gradient is not requested (only the mean's)
 #pragma unroll
@@ -645,7 +654,7 @@ __device__ inline float3 sh_backward(int deg, int M, float3 mean, float3 campos,
             if (i < M) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const float v = i < active ? basis[i] * dRGB[c] : 0.f;
+                    const float v = i < active ? basis[i] * sd.dRGB[c] : 0.f;
                     dL_dsh[i * 3 + c] = acc ? dL_dsh[i * 3 + c] + v : v;
                 }
             }
@@ -653,7 +662,7 @@ __device__ inline float3 sh_backward(int deg, int M, float3 mean, float3 campos,
         for (int i = 16; i < M; ++i)
             for (int c = 0; c < 3; ++c) dL_dsh[i * 3 + c] = acc ? dL_dsh[i * 3 + c] : 0.f;
     }
-    return unit_vec_bwd(d0, dL_ddir);
+    return unit_vec_bwd(sd.d0, dL_ddir);
 }
 
 __device__ inline void cov3d_backward(float3 s3, float mod, float4 q, const float *dc, float3 &dscale,
@@ -715,9 +724,11 @@ __device__ inline void add_chunk_records(const float *sf, uint32_t cb, uint32_t 
     }
 }
 
+// Gaussian i's records [goff[i], goff[i + 1]) (none for a lane past P) summed into acc.
 template <int C>  // records per staged chunk (the wave's LDS slice holds 3 C float4)
-__device__ inline void sum_records_span(uint32_t e0, uint32_t e1, const float4 *__restrict__ part,
-                                        float4 *stage, float (&acc)[kPartial]) {
+__device__ inline void sum_records(int i, int P, const uint32_t *__restrict__ goff, const float4 *__restrict__ part,
+                                   float4 *stage, float (&acc)[kPartial]) {
+    const uint32_t e0 = goff[min(i, P)], e1 = goff[min(i + 1, P)];  // both in flight at once
     const int lane = threadIdx.x & 63;
     const uint32_t E0 = __builtin_amdgcn_readfirstlane(e0);
     const uint32_t E1 = __builtin_amdgcn_readlane(e1, 63);
@@ -743,19 +754,6 @@ __device__ inline void sum_records_span(uint32_t e0, uint32_t e1, const float4 *
         add_chunk_records(sf, cb, max(e0, cb), min(e1, cb + C), acc);
         wave_lds_sync();
     }
-}
-template <int C>
-__device__ inline void sum_records_chunked(int i, int P, const uint32_t *__restrict__ goff,
-                                           const float4 *__restrict__ part, float4 *stage,
-                                           float (&acc)[kPartial]) {
-    const uint32_t e0 = goff[min(i, P)], e1 = goff[min(i + 1, P)];  // both in flight at once
-    sum_records_span<C>(e0, e1, part, stage, acc);
-}
-template <int MC>
-__device__ inline void sum_records_wave(int i, int P, const uint32_t *__restrict__ goff,
-                                        const float4 *__restrict__ part, float4 *stage,
-                                        float (&acc)[kPartial]) {
-    sum_records_chunked<kRecChunk<MC>>(i, P, goff, part, stage, acc);
 }
 
 // dL/dconic (acc[2..4]) and dL/dmeans2D (acc[0..1]) of one view -> dL/dcov3D (dcov, upper triangle)
@@ -838,197 +836,216 @@ __device__ inline void view_chain(float3 mean, const float (&c3)[6], const float
     dm2 += (pj[8] * m_w - pj[11] * mul1) * g2x + (pj[9] * m_w - pj[11] * mul2) * g2y;
 }
 
-// A Gaussian's inputs that k_gauss_bwd loads before its record walk (their latency overlaps it).
-struct GaussIn { int radius; float3 mean, s3; float4 q; float o; };
+// A Gaussian's parameters as the two per-Gaussian kernels hold them: the mean and the 3D covariance c3 --
+// given, or built from the scale and rotation (`built`), then with the activated scale s3, the quaternion q
+// it was built from and the raw quaternion's norm qn, which the gradient's chain rules need.
+struct GaussParams { float3 mean, s3; float4 q; float qn, c3[6]; bool built; };
+// The raw loads of Gaussian i's parameters.  Both kernels issue them early -- k_gauss_bwd before its
+// record walk, k_gauss_bwd_multi before its SH row copy -- and run gauss_params_activate afterwards, so
+// the loads' latency overlaps that work.
+__device__ inline void gauss_params_load(GaussParams &p, int i, const float *means3D, const float *scales,
+                                         const float *rotations, const float *cov3D_precomp) {
+    p.mean = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
+    p.s3 = make_float3(0, 0, 0);
+    p.q = make_float4(0, 0, 0, 0);
+    p.qn = 0.f;
+    p.built = !cov3D_precomp;  // (a launch has either the covariances or scales and rotations)
+    if (cov3D_precomp) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) p.c3[k] = cov3D_precomp[6 * i + k];
+    } else {
+        p.s3 = make_float3(scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]);
+        p.q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
+    }
+}
+__device__ inline void gauss_params_activate(GaussParams &p, int act, float scale_modifier) {
+    if (!p.built) return;
+    // (expect-false: keeps the two wave-uniform branches.  Without the hint the compiler ran both
+    // activations in every launch and selected their results: k_gauss_bwd_multi +1 % alone)
+    if (__builtin_expect(act & GSR_ACT_EXP_SCALES, 0)) p.s3 = act_exp3(p.s3);
+    if (__builtin_expect(act & GSR_ACT_NORMALIZE_ROTATIONS, 0)) { p.qn = quat_norm(p.q); p.q = act_normalize(p.q, p.qn); }
+    cov3d_from_scale_rot(p.s3, scale_modifier, p.q, p.c3);
+}
 
-template <int MC>
-__device__ inline void gauss_bwd_one(
-    int i, int D, int M, int W, int H, float scale_modifier, float tan_fovx, float tan_fovy,
-    float h_x, float h_y, const float *__restrict__ means3D, const float *__restrict__ scales,
-    const float *__restrict__ rotations, const float *__restrict__ shs,
-    const float *__restrict__ cov3D_precomp, const float *__restrict__ viewmatrix,
-    const float *__restrict__ projmatrix, const float *__restrict__ campos, CamStrides cs,
-    const int *__restrict__ radii, const float (&acc)[kPartial], float *__restrict__ dL_dmeans2D,
-    float *__restrict__ dL_dcolors, float *__restrict__ dL_dopacity, float *__restrict__ dL_dmeans3D,
-    float *__restrict__ dL_dcov3D, float *__restrict__ dL_dsh, float *__restrict__ dL_dscales,
-    float *__restrict__ dL_drot, float *s_row, int act, const float4 *__restrict__ rec, int accm,
-    const uint8_t *__restrict__ clampm, const GaussIn &gi) {
-    // every output may be NULL (gradient not requested: the input does not require grad); accm:
-    // gsr_grad_bits of the outputs to add into instead of overwrite
-    const bool a2 = accm & GSR_GRAD_MEANS2D, ac = accm & GSR_GRAD_COLORS, ao = accm & GSR_GRAD_OPACITY,
-               a3 = accm & GSR_GRAD_MEANS3D, acv = accm & GSR_GRAD_COV3D, ash = accm & GSR_GRAD_SH,
-               asc = accm & GSR_GRAD_SCALES, ar = accm & GSR_GRAD_ROTATIONS;
-    if (!(gi.radius > 0)) {  // zero gradient: accumulated outputs keep their content
+// A Gaussian's gradients held in registers: its one view's (k_gauss_bwd) or the sums over the launch's
+// views (k_gauss_bwd_multi); dL/dcov3D is summed before the single cov3D -> scale / rotation chain, which is
+// linear in it.
+struct GaussGradVals { float opacity, color[3], mean[3], cov[6]; };
+// The tail of both per-Gaussian kernels: Gaussian i's gradients g go to the outputs o.  Every output may be
+// NULL (gradient not requested: the input does not require grad); an output whose o.accm bit is set is
+// added into, the others are overwritten.  vis: some view sees the Gaussian -- otherwise its gradient is
+// zero: zeros are stored and accumulated outputs keep their content.  o_act: the activated opacity from a
+// forward's record (sigmoid chain only).  dL/dmeans2D and dL/dSH are the callers' (one array per view; an
+// LDS row or global memory).
+__device__ inline void gauss_grads_store(const GaussGrads &o, int i, bool vis, const GaussGradVals &g,
+                                         const GaussParams &p, int act, float scale_modifier, float o_act) {
+    const int accm = o.accm;
+    const bool ac = accm & GSR_GRAD_COLORS, ao = accm & GSR_GRAD_OPACITY, a3 = accm & GSR_GRAD_MEANS3D,
+               acv = accm & GSR_GRAD_COV3D, asc = accm & GSR_GRAD_SCALES, ar = accm & GSR_GRAD_ROTATIONS;
+    if (!vis) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            if (dL_dmeans2D && !a2) dL_dmeans2D[3 * i + k] = 0.f;
-            if (dL_dmeans3D && !a3) dL_dmeans3D[3 * i + k] = 0.f;
-            if (dL_dcolors && !ac) dL_dcolors[3 * i + k] = 0.f;
-            if (dL_dscales && !asc) dL_dscales[3 * i + k] = 0.f;
+            if (o.dL_dmeans3D && !a3) o.dL_dmeans3D[3 * i + k] = 0.f;
+            if (o.dL_dcolors && !ac) o.dL_dcolors[3 * i + k] = 0.f;
+            if (o.dL_dscales && !asc) o.dL_dscales[3 * i + k] = 0.f;
         }
-        if (dL_dopacity && !ao) dL_dopacity[i] = 0.f;
-        if (dL_dcov3D && !acv) {
+        if (o.dL_dopacity && !ao) o.dL_dopacity[i] = 0.f;
+        if (o.dL_dcov3D && !acv) {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) dL_dcov3D[6 * i + k] = 0.f;
+            for (int k = 0; k < 6; ++k) o.dL_dcov3D[6 * i + k] = 0.f;
         }
-        if (dL_drot && !ar) {
+        if (o.dL_drot && !ar) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) dL_drot[4 * i + k] = 0.f;
+            for (int k = 0; k < 4; ++k) o.dL_drot[4 * i + k] = 0.f;
+        }
+        return;
+    }
+    float oo[1], oc[3], o3[3];  // old values of the outputs accumulated into, fetched together
+    old_load(o.dL_dopacity, (size_t)i, o.dL_dopacity && ao, oo);
+    old_load(o.dL_dcolors, 3 * (size_t)i, o.dL_dcolors && ac, oc);
+    old_load(o.dL_dmeans3D, 3 * (size_t)i, o.dL_dmeans3D && a3, o3);
+    if (!o.dL_dopacity) {
+    } else if (act & GSR_ACT_SIGMOID_OPACITY) {  // opacity = sigmoid(logit) when fused: d/dlogit = o (1 - o)
+        gput_old(o.dL_dopacity, i, g.opacity * ((1.f - o_act) * o_act), ao, oo[0]);
+    } else {
+        gput_old(o.dL_dopacity, i, g.opacity, ao, oo[0]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (o.dL_dcolors) gput_old(o.dL_dcolors, 3 * i + k, g.color[k], ac, oc[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (o.dL_dmeans3D) gput_old(o.dL_dmeans3D, 3 * i + k, g.mean[k], a3, o3[k]);
+    }
+    if (o.dL_dcov3D) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) gput(o.dL_dcov3D, 6 * i + k, g.cov[k], acv);
+    }
+    if (p.built) {
+        float os[3], orr[4];
+        old_load(o.dL_dscales, 3 * (size_t)i, o.dL_dscales && asc, os);
+        old_load(o.dL_drot, 4 * (size_t)i, o.dL_drot && ar, orr);
+        float3 ds; float4 dr;
+        cov3d_backward(p.s3, scale_modifier, p.q, g.cov, ds, dr);
+        if (act & GSR_ACT_EXP_SCALES) { ds.x *= p.s3.x; ds.y *= p.s3.y; ds.z *= p.s3.z; }
+        if (act & GSR_ACT_NORMALIZE_ROTATIONS) dr = act_normalize_bwd(p.q, p.qn, dr);
+        if (o.dL_dscales) {
+            gput_old(o.dL_dscales, 3 * i, ds.x, asc, os[0]); gput_old(o.dL_dscales, 3 * i + 1, ds.y, asc, os[1]);
+            gput_old(o.dL_dscales, 3 * i + 2, ds.z, asc, os[2]);
+        }
+        if (o.dL_drot) {
+            gput_old(o.dL_drot, 4 * i, dr.x, ar, orr[0]); gput_old(o.dL_drot, 4 * i + 1, dr.y, ar, orr[1]);
+            gput_old(o.dL_drot, 4 * i + 2, dr.z, ar, orr[2]); gput_old(o.dL_drot, 4 * i + 3, dr.w, ar, orr[3]);
+        }
+    } else {  // no scales or rotations to differentiate
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (o.dL_dscales && !asc) o.dL_dscales[3 * i + k] = 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (o.dL_drot && !ar) o.dL_drot[4 * i + k] = 0.f;
+        }
+    }
+}
+
+// k_gauss_bwd's arguments: one view's camera and saved state, the Gaussians' parameters, the outputs.
+struct GaussBwdArgs {
+    int P, D, M, act;
+    float scale_modifier, tan_fovx, tan_fovy, focal_x, focal_y;
+    const float *means3D, *scales, *rotations, *shs, *cov3D_precomp, *viewmatrix, *projmatrix, *campos;
+    CamStrides cs;
+    const int *radii; const uint32_t *goff; const float4 *part, *rec; const uint8_t *clampm;
+    float *dL_dmeans2D;
+    GaussGrads o;
+};
+
+// Gaussian i of k_gauss_bwd from its record sums acc: the view's chains, dL/dmeans2D and dL/dSH (s_row:
+// the Gaussian's LDS row when MC > 0, coefficients in, their gradient out), then the shared tail.
+template <int MC>
+__device__ inline void gauss_bwd_one(const GaussBwdArgs &a, int i, int radius, float o_act,
+                                     const float (&acc)[kPartial], GaussParams &p, float *s_row) {
+    const bool a2 = a.o.accm & GSR_GRAD_MEANS2D, ash = a.o.accm & GSR_GRAD_SH;
+    const int M = a.M;
+    float *dL_dsh = a.o.dL_dsh ? a.o.dL_dsh + (size_t)i * M * 3 : nullptr;  // (read when MC == 0)
+    const bool vis = radius > 0;
+    GaussGradVals g{};
+    if (!vis) {  // zero gradient: accumulated outputs keep their content
+        if (a.dL_dmeans2D && !a2) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.dL_dmeans2D[3 * i + k] = 0.f;
         }
         if (MC > 0) {
 #pragma unroll
             for (int k = 0; k < 3 * MC; ++k) s_row[k] = 0.f;
         } else if (dL_dsh && !ash) {
-            for (int k = 0; k < M * 3; ++k) dL_dsh[(size_t)i * M * 3 + k] = 0.f;
-        }
-        return;
-    }
-    {   // screen-space outputs: old values (accumulation) fetched together
-        float o2[3], oo[1], oc[3];
-        old_load(dL_dmeans2D, 3 * (size_t)i, dL_dmeans2D && a2, o2);
-        old_load(dL_dopacity, (size_t)i, dL_dopacity && ao, oo);
-        old_load(dL_dcolors, 3 * (size_t)i, dL_dcolors && ac, oc);
-        if (dL_dmeans2D) {
-            gput_old(dL_dmeans2D, 3 * i, acc[0], a2, o2[0]); gput_old(dL_dmeans2D, 3 * i + 1, acc[1], a2, o2[1]);
-            gput_old(dL_dmeans2D, 3 * i + 2, 0.f, a2, o2[2]);
-        }
-        // opacity = sigmoid(logit) when fused: d/dlogit = o (1 - o), o from the forward's record
-        if (!dL_dopacity) {
-        } else if (act & GSR_ACT_SIGMOID_OPACITY) {
-            const float o = gi.o;
-            gput_old(dL_dopacity, i, acc[5] * ((1.f - o) * o), ao, oo[0]);
-        } else {
-            gput_old(dL_dopacity, i, acc[5], ao, oo[0]);
-        }
-        if (dL_dcolors) {
-            gput_old(dL_dcolors, 3 * i, acc[6], ac, oc[0]); gput_old(dL_dcolors, 3 * i + 1, acc[7], ac, oc[1]);
-            gput_old(dL_dcolors, 3 * i + 2, acc[8], ac, oc[2]);
-        }
-    }
-    float vm[16], pj[16];
-    load_mat16(viewmatrix, cs.v0, cs.v1, vm);
-    load_mat16(projmatrix, cs.p0, cs.p1, pj);
-    const float3 mean = gi.mean;
-    float c3[6];
-    float3 s3 = make_float3(0, 0, 0);
-    float4 q = make_float4(0, 0, 0, 0);
-    float qn = 0.f;
-    if (cov3D_precomp) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) c3[k] = cov3D_precomp[6 * i + k];
-    } else {
-        s3 = gi.s3;
-        q = gi.q;
-        if (act & GSR_ACT_EXP_SCALES) s3 = act_exp3(s3);
-        if (act & GSR_ACT_NORMALIZE_ROTATIONS) { qn = quat_norm(q); q = act_normalize(q, qn); }
-        cov3d_from_scale_rot(s3, scale_modifier, q, c3);
-    }
-    float dcov[6], dm0, dm1, dm2;
-    view_chain(mean, c3, vm, pj, tan_fovx, tan_fovy, h_x, h_y, acc, dcov, dm0, dm1, dm2);
-    if (dL_dcov3D) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) gput(dL_dcov3D, 6 * i + k, dcov[k], acv);
-    }
-    if (MC > 0) {
-        bool cl[3];
-        const float3 cp = load_campos(campos, cs.c0);
-        clamp_from_mask(clampm[i], cl);  // the forward's clamp mask
-        const float3 d = sh_backward(D, MC, mean, cp, s_row, cl, make_float3(acc[6], acc[7], acc[8]), s_row);
-        dm0 += d.x; dm1 += d.y; dm2 += d.z;
-    } else if (shs) {
-        const float *sh = shs + (size_t)i * M * 3;
-        bool cl[3];
-        const float3 cp = load_campos(campos, cs.c0);
-        clamp_from_mask(clampm[i], cl);
-        const float3 d = sh_backward(D, M, mean, cp, sh, cl, make_float3(acc[6], acc[7], acc[8]),
-                                     dL_dsh ? dL_dsh + (size_t)i * M * 3 : nullptr, ash);
-        dm0 += d.x; dm1 += d.y; dm2 += d.z;
-    } else if (dL_dsh) {
-        if (!ash) for (int k = 0; k < M * 3; ++k) dL_dsh[(size_t)i * M * 3 + k] = 0.f;
-    }
-    const bool has_sr = scales && !cov3D_precomp;
-    float o3[3], os[3], orr[4];  // old values of the remaining accumulated outputs, fetched together
-    old_load(dL_dmeans3D, 3 * (size_t)i, dL_dmeans3D && a3, o3);
-    old_load(dL_dscales, 3 * (size_t)i, has_sr && dL_dscales && asc, os);
-    old_load(dL_drot, 4 * (size_t)i, has_sr && dL_drot && ar, orr);
-    if (dL_dmeans3D) {
-        gput_old(dL_dmeans3D, 3 * i, dm0, a3, o3[0]); gput_old(dL_dmeans3D, 3 * i + 1, dm1, a3, o3[1]);
-        gput_old(dL_dmeans3D, 3 * i + 2, dm2, a3, o3[2]);
-    }
-    if (has_sr) {
-        float3 ds; float4 dr;
-        cov3d_backward(s3, scale_modifier, q, dcov, ds, dr);
-        if (act & GSR_ACT_EXP_SCALES) { ds.x *= s3.x; ds.y *= s3.y; ds.z *= s3.z; }
-        if (act & GSR_ACT_NORMALIZE_ROTATIONS) dr = act_normalize_bwd(q, qn, dr);
-        if (dL_dscales) {
-            gput_old(dL_dscales, 3 * i, ds.x, asc, os[0]); gput_old(dL_dscales, 3 * i + 1, ds.y, asc, os[1]);
-            gput_old(dL_dscales, 3 * i + 2, ds.z, asc, os[2]);
-        }
-        if (dL_drot) {
-            gput_old(dL_drot, 4 * i, dr.x, ar, orr[0]); gput_old(dL_drot, 4 * i + 1, dr.y, ar, orr[1]);
-            gput_old(dL_drot, 4 * i + 2, dr.z, ar, orr[2]); gput_old(dL_drot, 4 * i + 3, dr.w, ar, orr[3]);
+            for (int k = 0; k < M * 3; ++k) dL_dsh[k] = 0.f;
         }
     } else {
-        if (dL_dscales && !asc) { dL_dscales[3 * i] = 0.f; dL_dscales[3 * i + 1] = 0.f; dL_dscales[3 * i + 2] = 0.f; }
-        if (dL_drot && !ar) { dL_drot[4 * i] = 0.f; dL_drot[4 * i + 1] = 0.f; dL_drot[4 * i + 2] = 0.f; dL_drot[4 * i + 3] = 0.f; }
+        if (a.dL_dmeans2D) {
+            float o2[3];
+            old_load(a.dL_dmeans2D, 3 * (size_t)i, a2, o2);
+            gput_old(a.dL_dmeans2D, 3 * i, acc[0], a2, o2[0]); gput_old(a.dL_dmeans2D, 3 * i + 1, acc[1], a2, o2[1]);
+            gput_old(a.dL_dmeans2D, 3 * i + 2, 0.f, a2, o2[2]);
+        }
+        g.opacity = acc[5]; g.color[0] = acc[6]; g.color[1] = acc[7]; g.color[2] = acc[8];
+        float vm[16], pj[16];
+        load_mat16(a.viewmatrix, a.cs.v0, a.cs.v1, vm);
+        load_mat16(a.projmatrix, a.cs.p0, a.cs.p1, pj);
+        gauss_params_activate(p, a.act, a.scale_modifier);
+        view_chain(p.mean, p.c3, vm, pj, a.tan_fovx, a.tan_fovy, a.focal_x, a.focal_y, acc, g.cov, g.mean[0],
+                   g.mean[1], g.mean[2]);
+        if (MC > 0 || a.shs) {
+            // (the forward's clamp mask)
+            const ShDir sd = sh_dir(p.mean, load_campos(a.campos, a.cs.c0), a.clampm[i], acc[6], acc[7], acc[8]);
+            float3 d;
+            if constexpr (MC > 0) d = sh_backward(a.D, MC, sd, s_row, s_row);
+            else d = sh_backward(a.D, M, sd, a.shs + (size_t)i * M * 3, dL_dsh, ash);
+            g.mean[0] += d.x; g.mean[1] += d.y; g.mean[2] += d.z;
+        } else if (dL_dsh && !ash) {
+            for (int k = 0; k < M * 3; ++k) dL_dsh[k] = 0.f;
+        }
     }
+    gauss_grads_store(a.o, i, vis, g, p, a.act, a.scale_modifier, o_act);
 }
 
 template <int MC>  // SH coefficient count staged through LDS (0: direct global access / no SH)
-__global__ __launch_bounds__(256) void k_gauss_bwd(
-    int P, int D, int M, int W, int H, float scale_modifier, float tan_fovx, float tan_fovy,
-    float h_x, float h_y, const float *__restrict__ means3D, const float *__restrict__ scales,
-    const float *__restrict__ rotations, const float *__restrict__ shs,
-    const float *__restrict__ cov3D_precomp, const float *__restrict__ viewmatrix,
-    const float *__restrict__ projmatrix, const float *__restrict__ campos, CamStrides cs,
-    const int *__restrict__ radii, const uint32_t *__restrict__ goff,
-    const float4 *__restrict__ part, float *__restrict__ dL_dmeans2D,
-    float *__restrict__ dL_dcolors, float *__restrict__ dL_dopacity, float *__restrict__ dL_dmeans3D,
-    float *__restrict__ dL_dcov3D, float *__restrict__ dL_dsh, float *__restrict__ dL_dscales,
-    float *__restrict__ dL_drot, int act, const float4 *__restrict__ rec, int accm,
-    const uint8_t *__restrict__ clampm) {
+__global__ __launch_bounds__(256) void k_gauss_bwd(const GaussBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float s_sh[];
     constexpr int RL = 3 * MC, RS = sh_row_stride(MC);
+    const int P = a.P;
     const int i0 = blockIdx.x * kShBlock;
     const int nrow = min(kShBlock, P - i0);
     const int i = i0 + threadIdx.x;
     // the Gaussian's radius, parameters and activated opacity are loaded first (clamped index for the
     // tail lanes), so their latency overlaps the record walk instead of following it
     const int ic = min(i, P - 1);
-    GaussIn gi;
-    gi.radius = radii[ic];
-    gi.mean = make_float3(means3D[3 * ic], means3D[3 * ic + 1], means3D[3 * ic + 2]);
-    gi.s3 = make_float3(0.f, 0.f, 0.f);
-    gi.q = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!cov3D_precomp) {
-        gi.s3 = make_float3(scales[3 * ic], scales[3 * ic + 1], scales[3 * ic + 2]);
-        gi.q = make_float4(rotations[4 * ic], rotations[4 * ic + 1], rotations[4 * ic + 2], rotations[4 * ic + 3]);
-    }
-    gi.o = (act & GSR_ACT_SIGMOID_OPACITY) && dL_dopacity ? rec[(size_t)kRecF4 * ic + 1].y : 0.f;
+    const int radius = a.radii[ic];
+    GaussParams p;
+    gauss_params_load(p, ic, a.means3D, a.scales, a.rotations, a.cov3D_precomp);
+    const float o_act = (a.act & GSR_ACT_SIGMOID_OPACITY) && a.o.dL_dopacity ? a.rec[(size_t)kRecF4 * ic + 1].y : 0.f;
     // the record sums, each wave in its own slice of the block's LDS (which the SH rows reuse)
     float acc[kPartial];
-    sum_records_wave<MC>(i, P, goff, part, reinterpret_cast<float4 *>(s_sh) + (threadIdx.x >> 6) * kRecStageF4<MC>, acc);
+    sum_records<kRecChunk<MC>>(i, P, a.goff, a.part,
+                               reinterpret_cast<float4 *>(s_sh) + (threadIdx.x >> 6) * kRecStageF4<MC>, acc);
     if constexpr (MC > 0) {  // coalesced copy of this block's SH rows into LDS (reused for dL/dSH)
         __syncthreads();
-        sh_rows_to_lds<MC>(shs + (size_t)i0 * RL, nrow, s_sh);
+        sh_rows_to_lds<MC>(a.shs + (size_t)i0 * RL, nrow, s_sh);
         __syncthreads();
     }
-    if (i < P) gauss_bwd_one<MC>(i, D, M, W, H, scale_modifier, tan_fovx, tan_fovy, h_x, h_y, means3D,
-                                 scales, rotations, shs, cov3D_precomp, viewmatrix, projmatrix, campos, cs,
-                                 radii, acc, dL_dmeans2D, dL_dcolors, dL_dopacity,
-                                 dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drot, s_sh + threadIdx.x * RS,
-                                 act, rec, accm, clampm, gi);
+    if (i < P) gauss_bwd_one<MC>(a, i, radius, o_act, acc, p, s_sh + threadIdx.x * RS);
     if constexpr (MC > 0) {  // coalesced store of the dL/dSH rows
-        if (!dL_dsh) return;
+        if (!a.o.dL_dsh) return;
         __syncthreads();
-        if (accm & GSR_GRAD_SH) sh_rows_from_lds<MC, true>(s_sh, nrow, dL_dsh + (size_t)i0 * RL);
-        else sh_rows_from_lds<MC, false>(s_sh, nrow, dL_dsh + (size_t)i0 * RL);
+        if (a.o.accm & GSR_GRAD_SH) sh_rows_from_lds<MC, true>(s_sh, nrow, a.o.dL_dsh + (size_t)i0 * RL);
+        else sh_rows_from_lds<MC, false>(s_sh, nrow, a.o.dL_dsh + (size_t)i0 * RL);
     }
 }
 
 // ---- per-view record sums (gsr_backward_render, deferred views) ---------------------------------
 // One thread per Gaussian, its wave's record span staged through LDS in 128-record chunks
-// (sum_records_span: lane-contiguous coalesced loads, each lane adding its own records in emission
+// (sum_records: lane-contiguous coalesced loads, each lane adding its own records in emission
 // order -- the same additions in the same order as k_gauss_bwd's walk), stored as kPartial x P SoA:
 // the multi-view pass then reads 9 coalesced words per Gaussian and view.  Few registers and 6 KB
 // of LDS per wave, so the walk's LDS round trips hide behind other waves; it runs on the view's
@@ -1065,7 +1082,7 @@ __global__ __launch_bounds__(256) void k_sum_records(int P, const uint32_t *__re
         reinterpret_cast<uint32_t *>(sums)[(size_t)kPartial * P] = camera_key(viewmatrix, projmatrix, campos, cs, W, H);
     const int i = blockIdx.x * 256 + threadIdx.x;
     float acc[kPartial];
-    sum_records_chunked<kSumChunk>(i, P, goff, part, s_stage + (threadIdx.x >> 6) * 3 * kSumChunk, acc);
+    sum_records<kSumChunk>(i, P, goff, part, s_stage + (threadIdx.x >> 6) * 3 * kSumChunk, acc);
     if (i < P) {
 #pragma unroll
         for (int k = 0; k < kPartial; ++k) sums[(size_t)k * P + i] = acc[k];
@@ -1125,18 +1142,9 @@ __global__ __launch_bounds__(kShBlock) GSR_MV_ATTR void k_gauss_bwd_multi(const 
     auto vid = [ord](int t) { return (int)((ord >> (4 * t)) & 15u); };  // the view summed t-th
     // the Gaussian's own parameters and the first view's record sums and radius are loaded before the
     // SH row copy, so that their latency overlaps it instead of following its barrier
-    const float3 mean = make_float3(a.means3D[3 * ii], a.means3D[3 * ii + 1], a.means3D[3 * ii + 2]);
-    float c3[6];
-    float3 s3 = make_float3(0, 0, 0);
-    float4 q = make_float4(0, 0, 0, 0);
-    float qn = 0.f;
-    if (a.cov3D_precomp) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) c3[k] = a.cov3D_precomp[6 * ii + k];
-    } else {
-        s3 = make_float3(a.scales[3 * ii], a.scales[3 * ii + 1], a.scales[3 * ii + 2]);
-        q = make_float4(a.rotations[4 * ii], a.rotations[4 * ii + 1], a.rotations[4 * ii + 2], a.rotations[4 * ii + 3]);
-    }
+    GaussParams p;
+    gauss_params_load(p, ii, a.means3D, a.scales, a.rotations, a.cov3D_precomp);
+    const float3 mean = p.mean;
     // each view's record sums (gsr_backward_render's k_sum_records, kPartial x P SoA: coalesced) and
     // radius are loaded one view ahead, so their latency hides behind the previous view's chains
     float nx[kPartial];
@@ -1147,13 +1155,8 @@ __global__ __launch_bounds__(kShBlock) GSR_MV_ATTR void k_gauss_bwd_multi(const 
         sh_rows_to_lds<MC>(a.shs + (size_t)i0 * RL, nrow, s_sh);
         __syncthreads();
     }
-    if (!a.cov3D_precomp) {
-        if (a.act & GSR_ACT_EXP_SCALES) s3 = act_exp3(s3);
-        if (a.act & GSR_ACT_NORMALIZE_ROTATIONS) { qn = quat_norm(q); q = act_normalize(q, qn); }
-        cov3d_from_scale_rot(s3, a.scale_modifier, q, c3);
-    }
-    float gm0 = 0.f, gm1 = 0.f, gm2 = 0.f, gop = 0.f, gc0 = 0.f, gc1 = 0.f, gc2 = 0.f;
-    float gcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    gauss_params_activate(p, a.act, a.scale_modifier);
+    GaussGradVals g{};  // the sums over the views
     bool vis = false;
     float o_act = 0.f;  // the activated opacity, from the record of a view that sees the Gaussian
     float m2[3] = {0.f, 0.f, 0.f};  // the screen-space gradient carried across views of one array
@@ -1204,94 +1207,23 @@ __global__ __launch_bounds__(kShBlock) GSR_MV_ATTR void k_gauss_bwd_multi(const 
         // the activated opacity (sigmoid chain only): written by every view that sees the Gaussian
         if (!vis && (a.act & GSR_ACT_SIGMOID_OPACITY)) o_act = V.rec[(size_t)kRecF4 * i + 1].y;
         vis = true;
-        gop += acc[5]; gc0 += acc[6]; gc1 += acc[7]; gc2 += acc[8];
+        g.opacity += acc[5]; g.color[0] += acc[6]; g.color[1] += acc[7]; g.color[2] += acc[8];
         float vm[16], pj[16];
         load_mat16(V.viewmatrix, V.cs.v0, V.cs.v1, vm);
         load_mat16(V.projmatrix, V.cs.p0, V.cs.p1, pj);
         float dcov[6], dm0, dm1, dm2;
-        view_chain(mean, c3, vm, pj, V.tan_fovx, V.tan_fovy, V.focal_x, V.focal_y, acc, dcov, dm0, dm1, dm2);
+        view_chain(mean, p.c3, vm, pj, V.tan_fovx, V.tan_fovy, V.focal_x, V.focal_y, acc, dcov, dm0, dm1, dm2);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) gcov[k] += dcov[k];
+        for (int k = 0; k < 6; ++k) g.cov[k] += dcov[k];
         if constexpr (MC > 0) {
-            const float3 cp = load_campos(V.campos, V.cs.c0);
-            bool cl[3];
-            clamp_from_mask(V.clampm[i], cl);  // the forward's clamp mask in this view
-            const float3 d0 = make_float3(mean.x - cp.x, mean.y - cp.y, mean.z - cp.z);
-            const float len = sqrtf(d0.x * d0.x + d0.y * d0.y + d0.z * d0.z);
-            const float x = d0.x / len, y = d0.y / len, z = d0.z / len;
-            const float dRGB[3] = {acc[6] * (cl[0] ? 0.f : 1.f), acc[7] * (cl[1] ? 0.f : 1.f),
-                                   acc[8] * (cl[2] ? 0.f : 1.f)};
-            const float3 d = unit_vec_bwd(d0, sh_dir_grad(a.D, x, y, z, s_row, dRGB));
+            // (the forward's clamp mask in this view)
+            const ShDir sd = sh_dir(mean, load_campos(V.campos, V.cs.c0), V.clampm[i], acc[6], acc[7], acc[8]);
+            const float3 d = unit_vec_bwd(sd.d0, sh_dir_grad(a.D, sd.x, sd.y, sd.z, s_row, sd.dRGB));
             dm0 += d.x; dm1 += d.y; dm2 += d.z;
         }
-        gm0 += dm0; gm1 += dm1; gm2 += dm2;
+        g.mean[0] += dm0; g.mean[1] += dm1; g.mean[2] += dm2;
     }
-    if (live) {
-        const int accm = a.accm;
-        const bool ac = accm & GSR_GRAD_COLORS, ao = accm & GSR_GRAD_OPACITY, a3 = accm & GSR_GRAD_MEANS3D,
-                   acv = accm & GSR_GRAD_COV3D, asc = accm & GSR_GRAD_SCALES, ar = accm & GSR_GRAD_ROTATIONS;
-        if (!vis) {  // no view sees it: zero gradient, accumulated outputs keep their content
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                if (a.dL_dmeans3D && !a3) a.dL_dmeans3D[3 * i + k] = 0.f;
-                if (a.dL_dcolors && !ac) a.dL_dcolors[3 * i + k] = 0.f;
-                if (a.dL_dscales && !asc) a.dL_dscales[3 * i + k] = 0.f;
-            }
-            if (a.dL_dopacity && !ao) a.dL_dopacity[i] = 0.f;
-            if (a.dL_dcov3D && !acv) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) a.dL_dcov3D[6 * i + k] = 0.f;
-            }
-            if (a.dL_drot && !ar) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) a.dL_drot[4 * i + k] = 0.f;
-            }
-        } else {
-            float oo[1], oc[3], o3[3];
-            old_load(a.dL_dopacity, (size_t)i, a.dL_dopacity && ao, oo);
-            old_load(a.dL_dcolors, 3 * (size_t)i, a.dL_dcolors && ac, oc);
-            old_load(a.dL_dmeans3D, 3 * (size_t)i, a.dL_dmeans3D && a3, o3);
-            if (!a.dL_dopacity) {
-            } else if (a.act & GSR_ACT_SIGMOID_OPACITY) {  // d/dlogit = o (1 - o), o from a forward's record
-                gput_old(a.dL_dopacity, i, gop * ((1.f - o_act) * o_act), ao, oo[0]);
-            } else {
-                gput_old(a.dL_dopacity, i, gop, ao, oo[0]);
-            }
-            if (a.dL_dcolors) {
-                gput_old(a.dL_dcolors, 3 * i, gc0, ac, oc[0]); gput_old(a.dL_dcolors, 3 * i + 1, gc1, ac, oc[1]);
-                gput_old(a.dL_dcolors, 3 * i + 2, gc2, ac, oc[2]);
-            }
-            if (a.dL_dmeans3D) {
-                gput_old(a.dL_dmeans3D, 3 * i, gm0, a3, o3[0]); gput_old(a.dL_dmeans3D, 3 * i + 1, gm1, a3, o3[1]);
-                gput_old(a.dL_dmeans3D, 3 * i + 2, gm2, a3, o3[2]);
-            }
-            if (a.dL_dcov3D) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) gput(a.dL_dcov3D, 6 * i + k, gcov[k], acv);
-            }
-            const bool has_sr = a.scales && !a.cov3D_precomp;
-            if (has_sr) {
-                float os[3], orr[4];
-                old_load(a.dL_dscales, 3 * (size_t)i, a.dL_dscales && asc, os);
-                old_load(a.dL_drot, 4 * (size_t)i, a.dL_drot && ar, orr);
-                float3 ds; float4 dr;
-                cov3d_backward(s3, a.scale_modifier, q, gcov, ds, dr);
-                if (a.act & GSR_ACT_EXP_SCALES) { ds.x *= s3.x; ds.y *= s3.y; ds.z *= s3.z; }
-                if (a.act & GSR_ACT_NORMALIZE_ROTATIONS) dr = act_normalize_bwd(q, qn, dr);
-                if (a.dL_dscales) {
-                    gput_old(a.dL_dscales, 3 * i, ds.x, asc, os[0]); gput_old(a.dL_dscales, 3 * i + 1, ds.y, asc, os[1]);
-                    gput_old(a.dL_dscales, 3 * i + 2, ds.z, asc, os[2]);
-                }
-                if (a.dL_drot) {
-                    gput_old(a.dL_drot, 4 * i, dr.x, ar, orr[0]); gput_old(a.dL_drot, 4 * i + 1, dr.y, ar, orr[1]);
-                    gput_old(a.dL_drot, 4 * i + 2, dr.z, ar, orr[2]); gput_old(a.dL_drot, 4 * i + 3, dr.w, ar, orr[3]);
-                }
-            } else {
-                if (a.dL_dscales && !asc) { a.dL_dscales[3 * i] = 0.f; a.dL_dscales[3 * i + 1] = 0.f; a.dL_dscales[3 * i + 2] = 0.f; }
-                if (a.dL_drot && !ar) { a.dL_drot[4 * i] = 0.f; a.dL_drot[4 * i + 1] = 0.f; a.dL_drot[4 * i + 2] = 0.f; a.dL_drot[4 * i + 3] = 0.f; }
-            }
-        }
-    }
+    if (live) gauss_grads_store(a, i, vis, g, p, a.act, a.scale_modifier, o_act);
     if constexpr (MC > 0) {
         // dL/dSH = sum over the views of basis(dir_v) x dRGB_v, summed in the lane's own LDS row: the
         // coefficients it held are no longer read (every view's direction gradient is done), and the
@@ -1312,7 +1244,7 @@ __global__ __launch_bounds__(kShBlock) GSR_MV_ATTR void k_gauss_bwd_multi(const 
                 const MultiView &V = a.v[vid(t)];
                 const int rv = rv_n;
                 const uint8_t cm = cm_n;
-                const float g[3] = {g_n[0], g_n[1], g_n[2]};
+                const float gv[3] = {g_n[0], g_n[1], g_n[2]};
                 if (t + 1 < a.nv) {
                     const MultiView &Vn = a.v[vid(t + 1)];
                     rv_n = Vn.radii[i];
@@ -1321,20 +1253,14 @@ __global__ __launch_bounds__(kShBlock) GSR_MV_ATTR void k_gauss_bwd_multi(const 
                     for (int c = 0; c < 3; ++c) g_n[c] = Vn.sums[(size_t)(6 + c) * P + i];
                 }
                 if (!(rv > 0)) continue;
-                const float3 cp = load_campos(V.campos, V.cs.c0);
-                bool cl[3];
-                clamp_from_mask(cm, cl);
-                const float3 d0 = make_float3(mean.x - cp.x, mean.y - cp.y, mean.z - cp.z);
-                const float len = sqrtf(d0.x * d0.x + d0.y * d0.y + d0.z * d0.z);
-                const float x = d0.x / len, y = d0.y / len, z = d0.z / len;
-                const float dRGB[3] = {g[0] * (cl[0] ? 0.f : 1.f), g[1] * (cl[1] ? 0.f : 1.f), g[2] * (cl[2] ? 0.f : 1.f)};
+                const ShDir sd = sh_dir(mean, load_campos(V.campos, V.cs.c0), cm, gv[0], gv[1], gv[2]);
                 float basis[16];
-                sh_basis16(x, y, z, basis);
+                sh_basis16(sd.x, sd.y, sd.z, basis);
 #pragma unroll
                 for (int k = 0; k < MC; ++k)
                     if (k < active) {
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) s_row[3 * k + c] += basis[k] * dRGB[c];
+                        for (int c = 0; c < 3; ++c) s_row[3 * k + c] += basis[k] * sd.dRGB[c];
                     }
             }
         }
@@ -1375,32 +1301,19 @@ hipError_t launch_render_bwd(const BwdArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int MC>
-static void gauss_bwd_mc(const BwdArgs &a, hipStream_t s) {
-    constexpr size_t lds = std::max(sizeof(float) * kShBlock * (MC ? sh_row_stride(MC) : 0),
-                                    sizeof(float4) * kRecStageF4<MC> * (kShBlock / 64));
-    k_gauss_bwd<MC><<<div_up(a.v.P, kShBlock), kShBlock, lds, s>>>(
-        a.v.P, a.v.D, a.v.M, a.v.W, a.v.H, a.v.scale_modifier, a.v.tan_fovx, a.v.tan_fovy, a.v.focal_x, a.v.focal_y,
-        a.v.means3D, a.v.scales, a.v.rotations, a.v.shs, a.v.cov3D_precomp, a.v.viewmatrix, a.v.projmatrix, a.v.campos, a.v.cs,
-        a.radii, a.goff, a.part, a.dL_dmeans2D, a.dL_dcolors, a.dL_dopacity,
-        a.dL_dmeans3D, a.dL_dcov3D, a.dL_dsh, a.dL_dscales, a.dL_drot, a.v.act, a.rec, a.accm, a.clampm);
-}
-
 hipError_t launch_gauss_bwd(const BwdArgs &a, hipStream_t s) {
-    if (a.v.P == 0) return hipSuccess;
-    switch (a.v.shs ? a.v.M : 0) {
-        case 16: gauss_bwd_mc<16>(a, s); break;
-        case 9: gauss_bwd_mc<9>(a, s); break;
-        case 4: gauss_bwd_mc<4>(a, s); break;
-        case 1: gauss_bwd_mc<1>(a, s); break;
-        default: gauss_bwd_mc<0>(a, s); break;
-    }
+    const ViewIn &v = a.v;
+    if (v.P == 0) return hipSuccess;
+    const GaussBwdArgs k{v.P, v.D, v.M, v.act, v.scale_modifier, v.tan_fovx, v.tan_fovy, v.focal_x, v.focal_y,
+                         v.means3D, v.scales, v.rotations, v.shs, v.cov3D_precomp, v.viewmatrix, v.projmatrix, v.campos,
+                         v.cs, a.radii, a.goff, a.part, a.rec, a.clampm, a.dL_dmeans2D, a};
+    with_sh_count(v.shs, v.M, [&](auto mc) {
+        constexpr int MC = decltype(mc)::value;
+        constexpr size_t lds = std::max(sizeof(float) * kShBlock * (MC ? sh_row_stride(MC) : 0),
+                                        sizeof(float4) * kRecStageF4<MC> * (kShBlock / 64));
+        k_gauss_bwd<MC><<<div_up(v.P, kShBlock), kShBlock, lds, s>>>(k);
+    });
     return hipGetLastError();
-}
-
-template <int MC>
-static void gauss_bwd_multi_mc(const MultiArgs &a, hipStream_t s) {
-    k_gauss_bwd_multi<MC><<<div_up(a.P, kShBlock), kShBlock, multi_lds_bytes<MC>(), s>>>(a);
 }
 
 hipError_t launch_sum_records(int P, const uint32_t *goff, const float4 *part, float *sums, hipStream_t s,
@@ -1414,13 +1327,10 @@ hipError_t launch_sum_records(int P, const uint32_t *goff, const float4 *part, f
 
 hipError_t launch_gauss_bwd_multi(const MultiArgs &a, hipStream_t s) {
     if (a.P == 0 || a.nv == 0) return hipSuccess;
-    switch (a.shs ? a.M : 0) {  // the caller checked M in {1, 4, 9, 16} when shs are given
-        case 16: gauss_bwd_multi_mc<16>(a, s); break;
-        case 9: gauss_bwd_multi_mc<9>(a, s); break;
-        case 4: gauss_bwd_multi_mc<4>(a, s); break;
-        case 1: gauss_bwd_multi_mc<1>(a, s); break;
-        default: gauss_bwd_multi_mc<0>(a, s); break;
-    }
+    with_sh_count(a.shs, a.M, [&](auto mc) {  // the caller checked M in {1, 4, 9, 16} when shs are given
+        constexpr int MC = decltype(mc)::value;
+        k_gauss_bwd_multi<MC><<<div_up(a.P, kShBlock), kShBlock, multi_lds_bytes<MC>(), s>>>(a);
+    });
     return hipGetLastError();
 }
 

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/gsr.h"  // gsr_activation bits
 
 namespace gsr {
@@ -247,6 +249,18 @@ struct ScratchLayout {
 // LDS at SH3, small enough to co-run with other streams' render kernels (256 was 2 % slower).
 constexpr int kShBlock = 128;
 __host__ __device__ constexpr int sh_row_stride(int MC) { return (3 * MC) | 1; }  // odd: no bank conflicts
+// The SH-staging kernels' template argument for a launch whose `shs` hold M coefficients per Gaussian (NULL:
+// none): launch(std::integral_constant<int, MC>), MC = M for a staged count, else 0.
+template <typename F>
+inline void with_sh_count(const float *shs, int M, F launch) {
+    switch (shs ? M : 0) {
+        case 16: launch(std::integral_constant<int, 16>()); break;
+        case 9: launch(std::integral_constant<int, 9>()); break;
+        case 4: launch(std::integral_constant<int, 4>()); break;
+        case 1: launch(std::integral_constant<int, 1>()); break;
+        default: launch(std::integral_constant<int, 0>()); break;
+    }
+}
 
 // Block copy of `nrow` SH rows (3 MC floats each, contiguous in global memory) into LDS rows of
 // stride sh_row_stride(MC).  The block's global span starts 16-byte aligned whenever the array does

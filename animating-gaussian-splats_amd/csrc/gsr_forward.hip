@@ -1323,25 +1323,16 @@ __global__ void k_mark_visible(int P, const float *__restrict__ means3D,
 // ==========================================================================================
 // host launchers
 // ==========================================================================================
-template <int MC>
-static void preprocess_mc(const FwdArgs &a, hipStream_t s) {
-    k_preprocess<MC><<<div_up(a.v.P, kShBlock), kShBlock, sizeof(float) * kShBlock * (MC ? sh_row_stride(MC) : 0), s>>>(
-        a.v.P, a.v.D, a.v.M, a.v.means3D, a.v.scales, a.v.scale_modifier, a.v.rotations, a.v.opacities, a.v.shs,
-        a.v.colors_precomp, a.v.cov3D_precomp, a.v.viewmatrix, a.v.projmatrix, a.v.campos, a.v.W, a.v.H, a.v.tan_fovx,
-        a.v.tan_fovy, a.v.focal_x, a.v.focal_y, a.v.gx, a.v.gy, a.radii, a.depth, a.rec, a.rect, a.tiles, a.v.act, a.v.cs,
-        a.tile_count, a.v.gx * a.v.gy, a.clampm);
-}
-
 hipError_t launch_preprocess(const FwdArgs &a, hipStream_t s) {
     if (a.v.P == 0) return hipSuccess;
-    const int mc = a.v.shs ? a.v.M : 0;
-    switch (mc) {
-        case 16: preprocess_mc<16>(a, s); break;
-        case 9: preprocess_mc<9>(a, s); break;
-        case 4: preprocess_mc<4>(a, s); break;
-        case 1: preprocess_mc<1>(a, s); break;
-        default: preprocess_mc<0>(a, s); break;
-    }
+    with_sh_count(a.v.shs, a.v.M, [&](auto mc) {
+        constexpr int MC = decltype(mc)::value;
+        k_preprocess<MC><<<div_up(a.v.P, kShBlock), kShBlock, sizeof(float) * kShBlock * (MC ? sh_row_stride(MC) : 0), s>>>(
+            a.v.P, a.v.D, a.v.M, a.v.means3D, a.v.scales, a.v.scale_modifier, a.v.rotations, a.v.opacities, a.v.shs,
+            a.v.colors_precomp, a.v.cov3D_precomp, a.v.viewmatrix, a.v.projmatrix, a.v.campos, a.v.W, a.v.H, a.v.tan_fovx,
+            a.v.tan_fovy, a.v.focal_x, a.v.focal_y, a.v.gx, a.v.gy, a.radii, a.depth, a.rec, a.rect, a.tiles, a.v.act, a.v.cs,
+            a.tile_count, a.v.gx * a.v.gy, a.clampm);
+    });
     return hipGetLastError();
 }
 

@@ -50,7 +50,14 @@ struct FwdArgs {
 // blocks of the speculative k_tile_sort launch (they loop over the device-side list count)
 constexpr int kSpecSortBlocks = 512;
 
-struct BwdArgs {
+// The per-Gaussian gradient outputs the two backward kernels share (NULL: not requested) and the
+// gsr_grad_bits of the outputs added into instead of overwritten (gsr_grads.accumulate).
+struct GaussGrads {
+    float *dL_dcolors, *dL_dopacity, *dL_dmeans3D, *dL_dcov3D, *dL_dsh, *dL_dscales, *dL_drot;
+    int accm;
+};
+
+struct BwdArgs : GaussGrads {
     ViewIn v;
     int K;
     const int *radii;
@@ -64,10 +71,7 @@ struct BwdArgs {
     float4 *part;
     // upstream gradient
     const float *dL_dcolor;
-    // outputs
-    float *dL_dmeans2D, *dL_dcolors, *dL_dopacity, *dL_dmeans3D, *dL_dcov3D, *dL_dsh, *dL_dscales,
-        *dL_drot;
-    int accm;  // gsr_grad_bits: outputs accumulated into instead of overwritten
+    float *dL_dmeans2D;  // the screen-space output (the others: GaussGrads)
     const uint32_t *spec_ok;  // speculative render half (pair count unknown): kernels return when the forward's speculation failed
 };
 
@@ -108,11 +112,10 @@ struct MultiView {
     float *dL_dmeans2D;     // the view's screen-space gradient (P,3) or NULL
     int acc2;               // add into dL_dmeans2D instead of overwriting
 };
-struct MultiArgs {
-    int P, D, M, nv, act, accm;
+struct MultiArgs : GaussGrads {
+    int P, D, M, nv, act;
     float scale_modifier;
     const float *means3D, *scales, *rotations, *shs, *cov3D_precomp;
-    float *dL_dcolors, *dL_dopacity, *dL_dmeans3D, *dL_dcov3D, *dL_dsh, *dL_dscales, *dL_drot;
     MultiView v[kMultiViews];
 };
 hipError_t launch_gauss_bwd_multi(const MultiArgs &a, hipStream_t s);

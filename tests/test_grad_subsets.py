@@ -2,8 +2,9 @@
 
 Any of the eight gradient outputs of the backward (include/gsr.h gsr_grads) may be NULL, may be marked
 ``accumulate`` (old + new) and, through the multi-view entry point, may be a fresh uninitialised array
-that the first launch overwrites.  The two per-Gaussian kernels (k_gauss_bwd / gauss_bwd_one and
-k_gauss_bwd_multi, csrc/gsr_backward.hip) gate their loads and stores on those pointers and bits, and the
+that the first launch overwrites.  The two per-Gaussian kernels (k_gauss_bwd and k_gauss_bwd_multi,
+csrc/gsr_backward.hip) gate their loads and stores on those pointers and bits -- dL/dmeans2D and dL/dSH each
+in its own code, the other six outputs in the tail both call (gauss_grads_store) -- and the
 Python side keeps matching books (``_C._grad_outputs``, ``needed=``, ``_try_defer``'s targets,
 ``_run_group``).  Every other parity test requests all eight outputs; here every form is run with subsets
 of them (``train_py``: the reference's own call site, train.py:155-163 freezes the Gaussians so only
@@ -313,12 +314,15 @@ def _render_half(G, v):
     return G["sums"][v]
 
 
-def _views_call(kind, dev, want, m2=None, views=VIEWS, accumulate_into=None, overwrite=()):
-    """gsr_backward_gaussians over the views; m2: per view None or (array, accumulate_means2D)."""
+def _views_call(kind, dev, want, m2=None, views=VIEWS, accumulate_into=None, overwrite=(), only=None):
+    """gsr_backward_gaussians over the views (only: the indices of those passed, default all); m2: per view
+    None or (array, accumulate_means2D)."""
     G = _gpu(kind, dev, views)
     t = G["t"]
     vs = []
     for v, (c, f) in enumerate(zip(G["cams"], G["fws"])):
+        if only is not None and v not in only:
+            continue
         d = {"viewmatrix": c.viewmatrix, "projmatrix": c.projmatrix, "tanfovx": c.tanfovx, "tanfovy": c.tanfovy,
              "image_height": H, "image_width": W, "campos": c.campos, "bg": c.bg, "radii": f["radii"],
              "geomBuffer": f["geom"], "scratch": _render_half(G, v), "num_rendered": f["K"]}
@@ -389,6 +393,37 @@ def test_multi_view_subsets(kind, subset, cuda):
             assert _same_bits(accd[k].cpu()[nv], old[k][nv]), REF[k]  # no view sees them: content kept
             _close(f"multi-accumulate {kind}/{subset} {REF[k]}", _np(accd[k]),
                    old[k].double().numpy() + sums(REF[k]))
+
+
+@gpu
+@pytest.mark.parametrize("kind", MULTI_KINDS)
+def test_one_view_launch_equals_single_view(kind, cuda):
+    """gsr_backward_gaussians over view 0 alone against gsr_backward of view 0, all eight outputs on both
+    routes.  Both kernels add the view's records in emission order, run the same chains on the sums and
+    store through one tail (gauss_grads_store), and k_gauss_bwd_multi adds its single view's values to +0:
+    every output is equal in value (torch.equal, not the bit patterns: a zero's sign may differ).  Plain,
+    the launch writing means2D into a NaN-filled array, and accumulating into the same random old values."""
+    ora = _oracle(kind)
+    assert P % 128 and int((~ora["vis"][0]).sum()) >= 40  # live tail lanes, rows of radius 0
+    one = _single(kind, cuda, "all", _C._NATIVE_PARTS)
+    m2 = [(_nan((P, 3), cuda), False), None, None]
+    out = _views_call(kind, cuda, ALL, m2, only=(0,))
+    assert out[M2D] is None
+    for k in range(8):
+        got = m2[0][0] if k == M2D else out[k]
+        assert got.shape == one[k].shape and torch.equal(got, one[k]), (kind, REF[k])
+    gen = torch.Generator().manual_seed(17)
+    old = {k: 1e-2 * torch.randn(_shape(kind, k), generator=gen) for k in sorted(_present(kind))}
+    acc1 = [old[k].to(cuda) if k in old else None for k in range(8)]
+    accv = [old[k].to(cuda) if k in old and k != M2D else None for k in range(8)]
+    m2 = [(old[M2D].to(cuda), True), None, None]
+    one = _backward1(kind, cuda, 0, ALL, accumulate_into=acc1)
+    out = _views_call(kind, cuda, ALL, m2, accumulate_into=accv, only=(0,))
+    for k in range(8):
+        got = m2[0][0] if k == M2D else out[k]
+        assert got.shape == one[k].shape and torch.equal(got, one[k]), (kind, "accumulate", REF[k])
+        if k in old:
+            assert one[k].data_ptr() == acc1[k].data_ptr() and not torch.equal(one[k].cpu(), old[k]), REF[k]
 
 
 @gpu
