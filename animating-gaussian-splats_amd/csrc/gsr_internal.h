@@ -159,7 +159,8 @@ hipError_t launch_deform_in_bwd(int P, int H, const float *im, const float *iq, 
 
 // deformation network residual blocks (gsr_resblock.hip): stats = mean1, invstd1, mean2, invstd2 (4 H)
 constexpr int kResblockAutoBlocks = 256;  // persistent workgroups when the caller sets no bound (one per CU; twice that for H <= 64)
-constexpr int kResblockMaxH = 128;
+constexpr int kResblockNarrowH = 128;  // up to here the weight stays in LDS; wider blocks walk 128-column blocks and k panels
+constexpr int kResblockMaxH = 512;
 struct ResblockWorkspace {  // byte offsets; the backward's also holds the two transient (P, H) gradients
     size_t partial_s, partial_w, sums, g_s, g_z1, total;
     ResblockWorkspace(int P, int H, int max_blocks, bool backward);

@@ -26,6 +26,10 @@
 //                            1), one H x H partial per workgroup; R = G W, then stage 2 writes g_z1 = R gelu'(bn1(y1))
 //                            and the column sums of g_z1 and g_z1 xhat1, stage 1 writes g_x = R + g_s.
 //   k_res_reduce_w           sums the dW partials in workgroup order.
+//
+// The above is H <= 128, where the whole weight stays in LDS.  128 < H <= 512 runs the k_res_*_wide kernels
+// further down (128-column blocks of the output, k panels of 128, dW in a kernel of its own) with the same
+// mathematics and the same k_res_stats, k_res_out, k_res_colsum and k_res_reduce_w.
 #include "gsr_common.h"
 #include "gsr_internal.h"
 #include "gsr_mlp.h"
@@ -452,6 +456,378 @@ __global__ __launch_bounds__(256) void k_res_reduce_w(int n, int nb, const float
     dW[i] = (float)s;
 }
 
+// ---- 128 < H <= 512 ------------------------------------------------------------------------------
+// An H x H weight no longer fits LDS and an H x H dW no longer fits a workgroup's registers, so the grid
+// gets a second dimension over 128-column blocks of the output and the reduction dimension is walked in
+// panels of 128: per panel the workgroup stages 64 x 128 of the left operand and 128 x 128 of the weight and
+// multiplies on into the same accumulators, so every output element is still one fmaf chain over ascending k.
+// Staging slot q of thread t is row (t >> 7) + 4 q of panel column t & 127: a thread's column is fixed within
+// a panel and its BatchNorm constants travel in registers with the prefetched values.
+//
+//   k_res_gemm_wide<PRO>     k_res_gemm for column block blockIdx.y; a column belongs to one block, so the
+//                            statistics partials keep their (workgroup along the rows, 3, H) layout.
+//   k_res_bwd_out_wide       k_res_bwd_out over column chunks of 128.
+//   k_res_bwd_r_wide<ST>     R = G W for column block blockIdx.y with the epilogues of k_res_bwd_gemm.
+//   k_res_bwd_w_wide<ST>     dW = G^T A: workgroup (row group, 128 x 128 block of dW) forms the G and A panels
+//                            of the block's columns per 64-row tile, each wave two 32 x 32 accumulators; one
+//                            partial per row group, summed by k_res_reduce_w in row-group order.
+namespace {
+constexpr int kPanel = 128, kPS = kPanel + 1;    // columns per block / k per panel; LDS row stride
+constexpr int kRowStep = kThreads / kPanel;      // rows between a thread's staging slots
+constexpr int kNX = kRows * kPanel / kThreads;   // staging slots per thread of a 64 x 128 panel
+constexpr int kNW = kPanel * kPanel / kThreads;  // ... of a 128 x 128 weight panel
+
+// base[r H + c] from the last row for r >= rows and from column 0 unless `cin` (c < H): an unconditional load, so a
+// thread's loads issue back to back without a branch each.  The value of a clamped slot is some element of the
+// matrix.  Where the slot's index along the reduction is past H it is replaced by 0 on its way into LDS (one
+// predicate per thread and panel, no mask per prefetched value kept alive across the multiply); a slot of a row
+// past P or of an output column past H only feeds results that are neither stored nor counted in a sum.
+__device__ inline float load_clamped(const float *base, int r, int rows, int H, int c, bool cin) {
+    return base[(unsigned)((r < rows ? r : rows - 1) * H + (cin ? c : 0))];
+}
+
+// the BatchNorm backward's constants of one column: mean, invstd, gamma invstd, dbeta / P, dgamma / P
+struct BnBack { float mean, invstd, scale, db, dg; };
+__device__ inline BnBack bn_back(const BnCols &bn, const float *sums, int c, int H, int P) {
+    BnBack k = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c < H) {
+        k.mean = bn.mean[c];
+        k.invstd = bn.invstd[c];
+        k.scale = bn.gamma[c] * k.invstd;
+        k.db = sums[c] / (float)P;
+        k.dg = sums[H + c] / (float)P;
+    }
+    return k;
+}
+__device__ inline float bn_back_apply(const BnBack &k, float g, float y) {
+    const float xh = (y - k.mean) * k.invstd;
+    return k.scale * ((g - k.db) - xh * k.dg);
+}
+}  // namespace
+
+template <bool PRO>
+__global__ __launch_bounds__(kThreads) void k_res_gemm_wide(int P, int H, int tiles, const float *__restrict__ X,
+                                                            const float *__restrict__ W, BnCols bn,
+                                                            float *__restrict__ Y, double *__restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) float s_lds[];
+    float *Xs = s_lds;              // kRows * kPS
+    float *Ws = Xs + kRows * kPS;   // kPanel * kPS, k-major: Ws[k][j] = W[col0 + j][k0 + k]
+    float *st = Ws + kPanel * kPS;  // 2 x (mean, M2) x kPanel: the two row halves of the tile
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, mt = w & 1, nt = w >> 1;
+    const int col0 = blockIdx.y * kPanel, panels = div_up(H, kPanel), KP = (H + 1) & ~1;
+    const int pc = t & (kPanel - 1), pr = t >> 7;
+    const bool live = col0 + nt * 32 < H;  // this wave's column tile holds a column of the matrix
+
+    float px[kNX], pw[kNW], bm = 0.f, bi = 0.f, bg = 0.f, bb = 0.f;
+    auto fetch = [&](int tile, int kp) {
+        const int k = kp * kPanel + pc;
+        const bool kin = k < H;
+        const float *xt = X + (size_t)tile * kRows * H, *wt = W + (size_t)col0 * H;  // uniform bases, 32-bit offsets
+        const int rows = P - tile * kRows, cols = H - col0;
+#pragma unroll
+        for (int q = 0; q < kNX; ++q) px[q] = load_clamped(xt, pr + q * kRowStep, rows, H, k, kin);
+#pragma unroll
+        for (int q = 0; q < kNW; ++q) pw[q] = load_clamped(wt, pr + q * kRowStep, cols, H, k, kin);
+        if (PRO && kin) { bm = bn.mean[k]; bi = bn.invstd[k]; bg = bn.gamma[k]; bb = bn.beta[k]; }
+    };
+    if ((int)blockIdx.x < tiles) fetch(blockIdx.x, 0);
+
+    double rn = 0.0, rmean = 0.0, rm2 = 0.0;  // thread t < 128: column col0 + t over this workgroup's tiles
+    const float *xa = Xs + (mt * 32 + (lane & 31)) * kPS + (lane >> 5);
+    const float *wb = Ws + (lane >> 5) * kPS + nt * 32 + (lane & 31);
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int row0 = tile * kRows;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int kp = 0; kp < panels; ++kp) {
+            const bool kin = kp * kPanel + pc < H;
+            lds_barrier();  // the previous panel has been consumed
+#pragma unroll
+            for (int q = 0; q < kNX; ++q) {
+                const int r = pr + q * kRowStep;
+                float v = px[q];
+                if (PRO) v = gelu_f(((v - bm) * bi) * bg + bb);
+                Xs[r * kPS + pc] = kin ? v : 0.f;
+            }
+#pragma unroll
+            for (int q = 0; q < kNW; ++q) Ws[pc * kPS + pr + q * kRowStep] = kin ? pw[q] : 0.f;
+            lds_barrier();
+            const bool last = kp + 1 == panels;
+            if (!last || tile + (int)gridDim.x < tiles) fetch(last ? tile + gridDim.x : tile, last ? 0 : kp + 1);
+            if (live) {
+                const int kn = KP - kp * kPanel < kPanel ? KP - kp * kPanel : kPanel;
+                for (int k = 0; k < kn; k += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[k], wb[k * kPS], acc, 0, 0, 0);
+            }
+        }
+        if (live) {
+            const int lc = nt * 32 + (lane & 31), col = col0 + lc;
+            const int rbase = row0 + mt * 32;
+            float sum = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rbase + acc_row(r, lane);
+                if (row < P) {
+                    if (col < H) Y[(size_t)row * H + col] = acc[r];
+                    sum += acc[r];
+                }
+            }
+            sum += __shfl_xor(sum, 32);
+            int nv = P - rbase;
+            nv = nv < 0 ? 0 : (nv > 32 ? 32 : nv);
+            const float mean = nv > 0 ? sum / (float)nv : 0.f;
+            float m2 = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float d = acc[r] - mean;
+                if (rbase + acc_row(r, lane) < P) m2 += d * d;
+            }
+            m2 += __shfl_xor(m2, 32);
+            if (lane < 32) {
+                st[(mt * 2 + 0) * kPanel + lc] = mean;
+                st[(mt * 2 + 1) * kPanel + lc] = m2;
+            }
+        }
+        lds_barrier();
+        if (t < kPanel && col0 + t < H) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                int nv = P - (row0 + h * 32);
+                nv = nv < 0 ? 0 : (nv > 32 ? 32 : nv);
+                chan(rn, rmean, rm2, (double)nv, (double)st[(h * 2 + 0) * kPanel + t], (double)st[(h * 2 + 1) * kPanel + t]);
+            }
+        }
+    }
+    if (t < kPanel && col0 + t < H) {
+        double *p = partial + (size_t)blockIdx.x * 3 * H + col0 + t;
+        p[0] = rn;
+        p[H] = rmean;
+        p[2 * H] = rm2;
+    }
+}
+
+// thread t takes column (t & 127) of each 128-column chunk and rows t >> 7, + 2, ...
+__global__ __launch_bounds__(kEwThreads) void k_res_bwd_out_wide(int P, int H, int tiles, const float *__restrict__ g_out,
+                                                                 const float *__restrict__ y2, const float *__restrict__ x,
+                                                                 BnCols bn, float *__restrict__ g_s,
+                                                                 double *__restrict__ partial) {
+    __shared__ double s_red[2][kEwThreads];
+    constexpr int RW = kEwThreads / kPanel;
+    const int t = threadIdx.x, rl = t >> 7;
+    for (int c0 = 0; c0 < H; c0 += kPanel) {
+        const int c = c0 + (t & (kPanel - 1));
+        const bool in = c < H;
+        const float m = in ? bn.mean[c] : 0.f, is = in ? bn.invstd[c] : 0.f, g = in ? bn.gamma[c] : 0.f, b = in ? bn.beta[c] : 0.f;
+        double s0 = 0.0, s1 = 0.0;
+        for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+            const int row0 = tile * kRows;
+            for (int r = rl; r < kRows; r += RW) {
+                const int row = row0 + r;
+                if (row < P && in) {
+                    const size_t i = (size_t)row * H + c;
+                    const float xh = (y2[i] - m) * is;
+                    const float gs = g_out[i] * gelu_grad((xh * g + b) + x[i]);
+                    g_s[i] = gs;
+                    s0 += (double)gs;
+                    s1 += (double)(gs * xh);
+                }
+            }
+        }
+        s_red[0][t] = s0;
+        s_red[1][t] = s1;
+        lds_barrier();
+        if (t < kPanel && in) {
+            double a0 = 0.0, a1 = 0.0;
+            for (int q = 0; q < RW; ++q) {
+                a0 += s_red[0][q * kPanel + t];
+                a1 += s_red[1][q * kPanel + t];
+            }
+            partial[((size_t)blockIdx.x * 2 + 0) * H + c] = a0;
+            partial[((size_t)blockIdx.x * 2 + 1) * H + c] = a1;
+        }
+        lds_barrier();  // s_red is free for the next chunk
+    }
+}
+
+// stages as k_res_bwd_gemm; grid (workgroups along the rows, column blocks of g_out)
+template <int STAGE>
+__global__ __launch_bounds__(kThreads) void k_res_bwd_r_wide(int P, int H, int tiles, const float *__restrict__ g_in,
+                                                             const float *__restrict__ yn, BnCols bnG,
+                                                             const float *__restrict__ sums, const float *__restrict__ a_in,
+                                                             BnCols bnA, const float *__restrict__ W,
+                                                             const float *__restrict__ g_s, float *__restrict__ g_out,
+                                                             double *__restrict__ partialS) {
+    extern __shared__ __attribute__((aligned(16))) float s_lds[];
+    float *Gs = s_lds;             // kRows * kPS
+    float *Wn = Gs + kRows * kPS;  // kPanel * kPS, as stored: Wn[j][k] = W[j0 + j][col0 + k]
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, mt = w & 1, nt = w >> 1;
+    const int col0 = blockIdx.y * kPanel, panels = div_up(H, kPanel), KP = (H + 1) & ~1;
+    const int pc = t & (kPanel - 1), pr = t >> 7;
+    const int lc = nt * 32 + (lane & 31), col = col0 + lc;
+    const bool live = col0 + nt * 32 < H;
+
+    float am = 0.f, ai = 0.f, ag = 0.f, ab = 0.f;  // stage 2: bn1 of this lane's output column
+    if (STAGE == 2 && col < H) { am = bnA.mean[col]; ai = bnA.invstd[col]; ag = bnA.gamma[col]; ab = bnA.beta[col]; }
+    double ps0 = 0.0, ps1 = 0.0;  // stage 2: this lane's rows of column col
+
+    float pg[kNX], py[kNX], pw[kNW];
+    BnBack kb = {0.f, 0.f, 0.f, 0.f, 0.f};
+    auto fetch = [&](int tile, int jp) {
+        const int j = jp * kPanel + pc;
+        const size_t base = (size_t)tile * kRows * H;  // uniform bases, 32-bit offsets
+        const float *gt = g_in + base, *yt = yn + base, *wt = W + (size_t)jp * kPanel * H + col0;
+        const int rows = P - tile * kRows, wrows = H - jp * kPanel;
+#pragma unroll
+        for (int q = 0; q < kNX; ++q) {
+            pg[q] = load_clamped(gt, pr + q * kRowStep, rows, H, j, j < H);
+            py[q] = load_clamped(yt, pr + q * kRowStep, rows, H, j, j < H);
+        }
+#pragma unroll
+        for (int q = 0; q < kNW; ++q) {
+            pw[q] = load_clamped(wt, pr + q * kRowStep, wrows, H, pc, col0 + pc < H);
+        }
+        kb = bn_back(bnG, sums, j, H, P);
+    };
+    if ((int)blockIdx.x < tiles) fetch(blockIdx.x, 0);
+
+    const float *ga = Gs + (mt * 32 + (lane & 31)) * kPS + (lane >> 5);
+    const float *wb = Wn + (lane >> 5) * kPS + lc;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int row0 = tile * kRows;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int jp = 0; jp < panels; ++jp) {
+            const bool jin = jp * kPanel + pc < H;
+            lds_barrier();  // the previous panel has been consumed
+#pragma unroll
+            for (int q = 0; q < kNX; ++q) {
+                const int r = pr + q * kRowStep;
+                Gs[r * kPS + pc] = jin ? bn_back_apply(kb, pg[q], py[q]) : 0.f;
+            }
+#pragma unroll
+            for (int q = 0; q < kNW; ++q) {
+                const int j = pr + q * kRowStep;
+                Wn[j * kPS + pc] = jp * kPanel + j < H ? pw[q] : 0.f;
+            }
+            lds_barrier();
+            const bool last = jp + 1 == panels;
+            if (!last || tile + (int)gridDim.x < tiles) fetch(last ? tile + gridDim.x : tile, last ? 0 : jp + 1);
+            if (live) {
+                const int jn = KP - jp * kPanel < kPanel ? KP - jp * kPanel : kPanel;
+                for (int j = 0; j < jn; j += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[j], wb[j * kPS], acc, 0, 0, 0);
+            }
+        }
+        if (col < H) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = row0 + mt * 32 + acc_row(r, lane);
+                if (row >= P) continue;
+                const size_t at = (size_t)row * H + col;
+                if (STAGE == 2) {
+                    const float xh = (a_in[at] - am) * ai;
+                    const float gz = acc[r] * gelu_grad(xh * ag + ab);
+                    g_out[at] = gz;
+                    ps0 += (double)gz;
+                    ps1 += (double)(gz * xh);
+                } else {
+                    g_out[at] = acc[r] + g_s[at];
+                }
+            }
+        }
+    }
+    if (STAGE == 2) {
+        double *red = (double *)s_lds;  // 2 row halves x 2 sums x kPanel, over the G panel
+        ps0 += __shfl_xor(ps0, 32);
+        ps1 += __shfl_xor(ps1, 32);
+        lds_barrier();  // every wave is done with the last panel
+        if (lane < 32) {
+            red[(mt * 2 + 0) * kPanel + lc] = ps0;
+            red[(mt * 2 + 1) * kPanel + lc] = ps1;
+        }
+        lds_barrier();
+        if (t < kPanel && col0 + t < H) {
+            partialS[((size_t)blockIdx.x * 2 + 0) * H + col0 + t] = red[t] + red[2 * kPanel + t];
+            partialS[((size_t)blockIdx.x * 2 + 1) * H + col0 + t] = red[kPanel + t] + red[3 * kPanel + t];
+        }
+    }
+}
+
+// grid (row groups, CB * CB blocks of dW): block blockIdx.y = jb * CB + kb is dW[128 jb .., 128 kb ..]
+template <int STAGE>
+__global__ __launch_bounds__(kThreads) void k_res_bwd_w_wide(int P, int H, int tiles, int CB, const float *__restrict__ g_in,
+                                                             const float *__restrict__ yn, BnCols bnG,
+                                                             const float *__restrict__ sums, const float *__restrict__ a_in,
+                                                             BnCols bnA, float *__restrict__ partialW) {
+    extern __shared__ __attribute__((aligned(16))) float s_lds[];
+    float *Gs = s_lds;             // kRows * kPS: columns j0 ..
+    float *As = Gs + kRows * kPS;  // kRows * kPS: columns k0 ..
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int j0 = ((int)blockIdx.y / CB) * kPanel, k0 = ((int)blockIdx.y % CB) * kPanel;
+    const int pc = t & (kPanel - 1), pr = t >> 7;
+    const int cj = j0 + pc, ck = k0 + pc;
+    const BnBack kb = bn_back(bnG, sums, cj, H, P);
+    float am = 0.f, ai = 0.f, ag = 0.f, ab = 0.f;  // stage 2: bn1 of column ck
+    if (STAGE == 2 && ck < H) { am = bnA.mean[ck]; ai = bnA.invstd[ck]; ag = bnA.gamma[ck]; ab = bnA.beta[ck]; }
+
+    f32x16 dw[2];  // 32 x 32 tiles w and w + 8 of the block's 4 x 4
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dw[q][r] = 0.f;
+
+    float pg[kNX], py[kNX], pa[kNX];
+    auto fetch = [&](int tile) {
+        const size_t base = (size_t)tile * kRows * H;  // uniform bases, 32-bit offsets
+        const float *gt = g_in + base, *yt = yn + base, *at = a_in + base;
+        const int rows = P - tile * kRows;
+#pragma unroll
+        for (int q = 0; q < kNX; ++q) {
+            pg[q] = load_clamped(gt, pr + q * kRowStep, rows, H, cj, cj < H);
+            py[q] = load_clamped(yt, pr + q * kRowStep, rows, H, cj, cj < H);
+            pa[q] = load_clamped(at, pr + q * kRowStep, rows, H, ck, ck < H);
+        }
+    };
+    if ((int)blockIdx.x < tiles) fetch(blockIdx.x);
+
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int row0 = tile * kRows;
+        lds_barrier();  // the previous tile has been consumed
+#pragma unroll
+        for (int q = 0; q < kNX; ++q) {
+            const int r = pr + q * kRowStep;
+            const bool rin = row0 + r < P;
+            float a = pa[q];
+            if (STAGE == 2) a = gelu_f(((a - am) * ai) * ag + ab);
+            Gs[r * kPS + pc] = rin && cj < H ? bn_back_apply(kb, pg[q], py[q]) : 0.f;
+            As[r * kPS + pc] = rin && ck < H ? a : 0.f;
+        }
+        lds_barrier();
+        if (tile + (int)gridDim.x < tiles) fetch(tile + gridDim.x);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int id = w + 8 * q, jt = id >> 2, kt = id & 3;
+            if (j0 + jt * 32 < H && k0 + kt * 32 < H) {
+                const float *ga = Gs + (lane >> 5) * kPS + jt * 32 + (lane & 31);
+                const float *ab2 = As + (lane >> 5) * kPS + kt * 32 + (lane & 31);
+#pragma unroll 4
+                for (int k = 0; k < kRows; k += 2)
+                    dw[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[k * kPS], ab2[k * kPS], dw[q], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int id = w + 8 * q, jt = id >> 2, kt = id & 3;
+        const int k = k0 + kt * 32 + (lane & 31);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = j0 + jt * 32 + acc_row(r, lane);
+            if (j < H && k < H) partialW[((size_t)blockIdx.x * H + j) * H + k] = dw[q][r];
+        }
+    }
+}
+
 // ---- host launchers --------------------------------------------------------------------------
 namespace {
 int res_nt(int H) { return div_up(H, 32); }
@@ -490,16 +866,60 @@ int resblock_blocks(int P, int H, int max_blocks) {
     return persistent_blocks(P, kRows, max_blocks, kResblockAutoBlocks * (H <= 64 ? 2 : 1));
 }
 int resblock_out_blocks(int P, int max_blocks) { return persistent_blocks(P, kRows, max_blocks, kOutBlocks); }
+
+// H > 128.  Workgroups along the rows of the forward and R = G W kernels: with the column blocks about one per CU
+// (their LDS admits no second).  Row groups of dW = G^T A: with the CB x CB blocks of dW about one workgroup per
+// CU as well, which bounds the dW partials by kResblockAutoBlocks x 128 x 128 floats (16 MB) for every H and P.
+bool wide(int H) { return H > kResblockNarrowH; }
+int wide_cb(int H) { return div_up(H, kPanel); }
+int wide_blocks(int P, int H, int max_blocks) {
+    return persistent_blocks(P, kRows, max_blocks, kResblockAutoBlocks / wide_cb(H));
+}
+int wide_groups(int P, int H, int max_blocks) {
+    return persistent_blocks(P, kRows, max_blocks, kResblockAutoBlocks / (wide_cb(H) * wide_cb(H)));
+}
+constexpr size_t kWideFwdLds = sizeof(float) * ((size_t)kRows * kPS + (size_t)kPanel * kPS + 4 * kPanel);
+constexpr size_t kWideRLds = sizeof(float) * ((size_t)kRows * kPS + (size_t)kPanel * kPS);
+constexpr size_t kWideWLds = sizeof(float) * ((size_t)2 * kRows * kPS);
+
+template <bool PRO>
+hipError_t gemm_wide(int nb, int P, int H, const float *X, const float *W, const BnCols &bn, float *Y, double *partial,
+                     hipStream_t s) {
+    return launch_lds(k_res_gemm_wide<PRO>, dim3(nb, wide_cb(H)), kThreads, kWideFwdLds, s, P, H, div_up(P, kRows), X, W,
+                      bn, Y, partial);
+}
+
+// stage STAGE of the backward: R = G W into g_out (unless NULL) and dW into dW (unless NULL)
+template <int STAGE>
+hipError_t bwd_wide(int nb, int ng, int P, int H, const float *g_in, const float *yn, const BnCols &bnG, const float *sums,
+                    const float *a_in, const BnCols &bnA, const float *W, const float *g_s, float *g_out, float *partialW,
+                    float *dW, double *partialS, hipStream_t s) {
+    const int tiles = div_up(P, kRows), cb = wide_cb(H);
+    if (g_out) {
+        hipError_t e = launch_lds(k_res_bwd_r_wide<STAGE>, dim3(nb, cb), kThreads, kWideRLds, s, P, H, tiles, g_in, yn, bnG,
+                                  sums, a_in, bnA, W, g_s, g_out, partialS);
+        if (e != hipSuccess) return e;
+    }
+    if (dW) {
+        hipError_t e = launch_lds(k_res_bwd_w_wide<STAGE>, dim3(ng, cb * cb), kThreads, kWideWLds, s, P, H, tiles, cb, g_in,
+                                  yn, bnG, sums, a_in, bnA, partialW);
+        if (e != hipSuccess) return e;
+        k_res_reduce_w<<<div_up(H * H, 256), 256, 0, s>>>(H * H, ng, partialW, dW);
+    }
+    return hipGetLastError();
+}
 }  // namespace
 
 ResblockWorkspace::ResblockWorkspace(int P, int H, int max_blocks, bool backward) {
-    const size_t nb = (size_t)resblock_blocks(P, H, max_blocks), no = (size_t)resblock_out_blocks(P, max_blocks);
+    const size_t nb = (size_t)(wide(H) ? wide_blocks(P, H, max_blocks) : resblock_blocks(P, H, max_blocks));
+    const size_t ng = wide(H) ? (size_t)wide_groups(P, H, max_blocks) : nb;  // dW partials
+    const size_t no = (size_t)resblock_out_blocks(P, max_blocks);
     const size_t h = (size_t)H, ph = (size_t)P * h;
     size_t o = 0;
     partial_s = o; o = align256(o + sizeof(double) * 3 * h * (nb > no ? nb : no));
     partial_w = sums = g_s = g_z1 = o;
     if (backward) {
-        partial_w = o; o = align256(o + sizeof(float) * nb * h * h);
+        partial_w = o; o = align256(o + sizeof(float) * ng * h * h);
         sums = o;      o = align256(o + sizeof(float) * 4 * h);
         g_s = o;       o = align256(o + sizeof(float) * ph);
         g_z1 = o;      o = align256(o + sizeof(float) * ph);
@@ -513,14 +933,15 @@ hipError_t launch_resblock_fwd(int P, int H, const float *x, const float *W1, co
                                float *running_mean2, float *running_var2, char *ws, int max_blocks, float *y1, float *y2,
                                float *out, float *stats, hipStream_t s) {
     const ResblockWorkspace L(P, H, max_blocks, false);
-    const int nb = resblock_blocks(P, H, max_blocks);
+    const int nb = wide(H) ? wide_blocks(P, H, max_blocks) : resblock_blocks(P, H, max_blocks);
     double *partial = (double *)(ws + L.partial_s);
     const BnCols none = {nullptr, nullptr, nullptr, nullptr};
     const BnCols bn1 = {stats, stats + H, gamma1, beta1}, bn2 = {stats + 2 * H, stats + 3 * H, gamma2, beta2};
-    hipError_t e = gemm<false>(nb, P, H, x, W1, none, y1, partial, s);
+    hipError_t e = wide(H) ? gemm_wide<false>(nb, P, H, x, W1, none, y1, partial, s)
+                           : gemm<false>(nb, P, H, x, W1, none, y1, partial, s);
     if (e != hipSuccess) return e;
     k_res_stats<<<H, 64, 0, s>>>(P, H, nb, partial, eps1, momentum1, stats, stats + H, running_mean1, running_var1);
-    e = gemm<true>(nb, P, H, y1, W2, bn1, y2, partial, s);
+    e = wide(H) ? gemm_wide<true>(nb, P, H, y1, W2, bn1, y2, partial, s) : gemm<true>(nb, P, H, y1, W2, bn1, y2, partial, s);
     if (e != hipSuccess) return e;
     k_res_stats<<<H, 64, 0, s>>>(P, H, nb, partial, eps2, momentum2, stats + 2 * H, stats + 3 * H, running_mean2, running_var2);
     const size_t n = (size_t)P * H;
@@ -546,6 +967,24 @@ hipError_t launch_resblock_bwd(int P, int H, const float *x, const float *y1, co
     float *g_s = (float *)(ws + L.g_s), *g_z1 = (float *)(ws + L.g_z1);
     const BnCols bn1 = {stats, stats + H, gamma1, beta1}, bn2 = {stats + 2 * H, stats + 3 * H, gamma2, beta2};
     const bool below = dx || dW1 || dgamma1 || dbeta1;  // anything past a1
+    if (wide(H)) {
+        const int nw = wide_blocks(P, H, max_blocks), ng = wide_groups(P, H, max_blocks);
+        k_res_bwd_out_wide<<<no, kEwThreads, 0, s>>>(P, H, tiles, g_out, y2, x, bn2, g_s, partial_s);
+        k_res_colsum<<<H, 64, 0, s>>>(H, no, partial_s, sums, dbeta2, dgamma2);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if (dW2 || below) {
+            e = bwd_wide<2>(nw, ng, P, H, g_s, y2, bn2, sums, y1, bn1, W2, nullptr, below ? g_z1 : nullptr, partial_w, dW2,
+                            partial_s, s);
+            if (e != hipSuccess) return e;
+            if (below) k_res_colsum<<<H, 64, 0, s>>>(H, nw, partial_s, sums + 2 * H, dbeta1, dgamma1);
+        }
+        if (dx || dW1) {
+            e = bwd_wide<1>(nw, ng, P, H, g_z1, y1, bn1, sums + 2 * H, x, bn1, W1, g_s, dx, partial_w, dW1, nullptr, s);
+            if (e != hipSuccess) return e;
+        }
+        return hipGetLastError();
+    }
     int CW = 8;
     while (CW < H) CW <<= 1;
     k_res_bwd_out<<<no, kEwThreads, 0, s>>>(P, H, tiles, CW, g_out, y2, x, bn2, g_s, partial_s);

@@ -12,14 +12,17 @@ Gaussian (csrc/gsr_deform.hip), and its backward recomputes the features for ``d
   to ``[enc(initial) | enc(previous) | enc(progress)]``; gradients flow to ``weight`` and ``bias`` only
   (the reference detaches the encoded parameters, train.py:255-258);
 * ``residual_block(x, fc1_weight, bn1, fc2_weight, bn2)`` -- one ResidualBlock (train.py:57-77) with
-  training-mode BatchNorm, fused (csrc/gsr_resblock.hip): three (P, H) tensors stay alive for the backward;
-  ``set_fused_residual_blocks(False)`` sends ``ResidualBlock`` back to the torch ops;
+  training-mode BatchNorm, fused (csrc/gsr_resblock.hip) for H <= 512: three (P, H) tensors stay alive for
+  the backward; ``set_fused_residual_blocks(False)`` sends ``ResidualBlock`` back to the torch ops, and
+  ``set_fused_residual_block_width(max_hidden)`` sets the widest H that ``ResidualBlock`` routes to the
+  kernels by itself (128 by default, up to 512);
 * ``deform_output_layer(x, weight, bias, initial_params)`` -- ``fc_out`` and the ``+ [initial means | initial
   quaternions]`` that follows it (train.py:106-108) in one kernel (csrc/gsr_head.hip), the (P, 7) concatenation
   never built; gradients flow to ``x``, ``weight`` and ``bias`` (and to the initial values if they require one);
   ``set_fused_output_head(False)`` sends ``DeformationNetwork`` back to the two torch lines;
 * ``DeformationNetwork`` -- train.py:80-110 with the reference's ``state_dict`` names and shapes; its
-  residual blocks run fused when eligible (training mode, H <= 128), its output head in either mode;
+  residual blocks run fused when eligible (training mode, H <= the fused width, 128 by default), its
+  output head in either mode;
 * ``update_gaussian_cloud_parameters`` -- train.py:269-308; the ``* 0.01`` update stays in torch.
 
 All fp32.  There is no CPU path: CPU tensors raise.
@@ -32,11 +35,12 @@ from torch import nn
 from diff_gaussian_rasterization import _C
 
 __all__ = ["encode_means_and_rotations", "encoding_ranges", "deform_input_layer", "residual_block",
-           "set_fused_residual_blocks", "deform_output_layer", "set_fused_output_head", "ResidualBlock",
-           "DeformationNetwork", "update_gaussian_cloud_parameters", "MAX_HIDDEN", "MAX_FUSED_HIDDEN"]
+           "set_fused_residual_blocks", "set_fused_residual_block_width", "deform_output_layer",
+           "set_fused_output_head", "ResidualBlock", "DeformationNetwork", "update_gaussian_cloud_parameters",
+           "MAX_HIDDEN", "MAX_FUSED_HIDDEN"]
 
 MAX_HIDDEN = 512
-MAX_FUSED_HIDDEN = 128  # widest hidden dimension of the fused residual blocks (wider ones run the torch ops)
+MAX_FUSED_HIDDEN = 128  # widest hidden dimension ResidualBlock sends to the fused kernels by default
 ENCODING_WIDTH = 92  # 3 means x 10 frequencies x (sin, cos) + 4 quaternion components x 4 x 2
 INPUT_WIDTH = 192    # two encodings + the 8 progress columns
 RANGE_BLOCKS = 256   # GSR_POSENC_RANGE_BLOCKS of include/gsr.h
@@ -206,6 +210,21 @@ def set_fused_residual_blocks(on):
     return previous
 
 
+_FUSED_RESBLOCK_WIDTH = MAX_FUSED_HIDDEN
+
+
+def set_fused_residual_block_width(max_hidden):
+    """The widest hidden dimension at which ``ResidualBlock.forward`` runs eligible calls on the fused kernels:
+    ``MAX_FUSED_HIDDEN`` (128, the default) to ``MAX_HIDDEN`` (512); wider blocks run the torch ops.  An explicit
+    ``residual_block`` call runs the kernels at any H <= 512, and ``set_fused_residual_blocks(False)`` wins over
+    this.  Process-wide (the A/B switch of tools/bench_resblock.py's wide legs); returns the previous value."""
+    global _FUSED_RESBLOCK_WIDTH
+    if isinstance(max_hidden, bool) or not isinstance(max_hidden, int) or not MAX_FUSED_HIDDEN <= max_hidden <= MAX_HIDDEN:
+        raise ValueError(f"set_fused_residual_block_width: {max_hidden!r} outside [{MAX_FUSED_HIDDEN}, {MAX_HIDDEN}]")
+    previous, _FUSED_RESBLOCK_WIDTH = _FUSED_RESBLOCK_WIDTH, max_hidden
+    return previous
+
+
 class _ResBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, g1, b1, w2, g2, b2, bn1, bn2, max_blocks, save):
@@ -251,13 +270,14 @@ def _check_bn(bn, H, name):
 
 def residual_block(x, fc1_weight, bn1, fc2_weight, bn2, max_blocks=0):
     """One ResidualBlock of train.py:57-77 on the kernels of csrc/gsr_resblock.hip:
-    ``gelu(bn2(gelu(bn1(x @ fc1_weight.T)) @ fc2_weight.T) + x)`` for ``x`` (P >= 2, H <= 128) float32 on
+    ``gelu(bn2(gelu(bn1(x @ fc1_weight.T)) @ fc2_weight.T) + x)`` for ``x`` (P >= 2, H <= 512) float32 on
     the GPU, ``fc*_weight`` (H, H) and ``bn*`` the two ``nn.BatchNorm1d`` modules, always normalising with
     the batch statistics (training mode).  Their running statistics are blended and
     ``num_batches_tracked`` incremented as ``F.batch_norm`` does.  Gradients flow to ``x``, both weights and
     both BatchNorms' affine parameters; the graph keeps ``x``, the two GEMM outputs and 4 H statistics.
-    ``max_blocks``: upper bound on the persistent workgroups (0: automatic)."""
-    P, H = _check_activation(x, "residual_block", MAX_FUSED_HIDDEN)
+    ``max_blocks``: upper bound on the persistent workgroups along the rows (0: automatic).  H <= 128 keeps
+    the weights in LDS; wider blocks run the kernels that walk 128-column blocks and k panels."""
+    P, H = _check_activation(x, "residual_block", MAX_HIDDEN)
     if P < 2:
         raise ValueError(f"residual_block: batch statistics need more than one row (got {P})")
     for w, name in ((fc1_weight, "fc1_weight"), (fc2_weight, "fc2_weight")):
@@ -280,8 +300,9 @@ def residual_block(x, fc1_weight, bn1, fc2_weight, bn2, max_blocks=0):
 
 
 class ResidualBlock(nn.Module):
-    """train.py:57-77.  A training-mode call on a contiguous float32 GPU (P >= 2, H <= 128) input runs
-    ``residual_block`` (unless ``set_fused_residual_blocks(False)``); every other call the torch ops."""
+    """train.py:57-77.  A training-mode call on a contiguous float32 GPU (P >= 2, H <= 128, or up to what
+    ``set_fused_residual_block_width`` allows) input runs ``residual_block`` (unless
+    ``set_fused_residual_blocks(False)``); every other call the torch ops."""
 
     def __init__(self, dimension):
         super().__init__()
@@ -292,7 +313,7 @@ class ResidualBlock(nn.Module):
 
     def _fused(self, x):
         if not (_FUSED_RESBLOCKS and self.training and x.dim() == 2 and x.shape[0] >= 2
-                and x.shape[1] <= MAX_FUSED_HIDDEN):
+                and x.shape[1] <= _FUSED_RESBLOCK_WIDTH):
             return False
         if tuple(self.fc1.weight.shape) != (x.shape[1],) * 2 or tuple(self.fc2.weight.shape) != (x.shape[1],) * 2:
             return False

@@ -457,7 +457,7 @@ int gsr_deform_in_backward(int P, int H, const float *initial_means, const float
                            float *dL_dbias, void *stream);
 
 /* ---- Deformation network residual blocks (additive to ABI 21) -----------------------------------
- * One ResidualBlock of train.py:57-77 on x (P, H) fp32 row-major, 2 <= P, 1 <= H <= 128:
+ * One ResidualBlock of train.py:57-77 on x (P, H) fp32 row-major, 2 <= P, 1 <= H <= 512:
  *     y1 = x fc1_weight^T;  a1 = gelu(bn1(y1));  y2 = a1 fc2_weight^T;  out = gelu(bn2(y2) + x)
  * fc*_weight (H, H) as in nn.Linear(H, H, bias=False); bn* in training mode: normalised with the batch
  * mean and the biased batch variance (Chan's formula in double over per-workgroup (count, mean, M2)
@@ -469,8 +469,11 @@ int gsr_deform_in_backward(int P, int H, const float *initial_means, const float
  * dL_dfc*_weight (H, H), dL_dbn*_weight / _bias (H)); the others are not computed.  workspace:
  * gsr_resblock_workspace_bytes(P, H, max_blocks, backward) bytes of device memory (the backward's holds
  * two transient (P, H) gradients), not kept between the two calls.  max_blocks > 0: at most that many
- * persistent workgroups (0: automatic).  No float atomics: every row reduction is one partial per
- * workgroup summed in workgroup order, two runs are bitwise equal. */
+ * persistent workgroups along the rows (0: automatic).  No float atomics: every row reduction is one
+ * partial per workgroup summed in workgroup order, two runs are bitwise equal.  H <= 128 keeps the whole
+ * weight in LDS; 128 < H <= 512 walks 128-column blocks of the output and k panels of 128 (every output
+ * element still one fmaf chain over ascending k) and computes dW in kernels of their own, whose partials
+ * stay within 16 MB (the backward's workspace beyond the two transient gradients within 64 MB) for any P. */
 size_t gsr_resblock_workspace_bytes(int P, int H, int max_blocks, int backward);
 int gsr_resblock_forward(int P, int H, const float *x, const float *fc1_weight, const float *bn1_weight,
                          const float *bn1_bias, const float *fc2_weight, const float *bn2_weight,

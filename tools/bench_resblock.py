@@ -2,6 +2,7 @@
 Writes one JSON file (default profiles/resblock_ab.json).
 
     python tools/bench_resblock.py               # P = 1M, H = 64 and 128
+    python tools/bench_resblock.py --wide        # P = 1M, H = 256 and 512 -> profiles/resblock_wide_ab.json
 
 Per hidden dimension: one ``splat_deform.ResidualBlock`` in training mode on a (P, H) N(0, 1) input that
 requires a gradient (inside the network it is fc_in's output), with an N(0, 1) upstream gradient.  The fused
@@ -11,6 +12,11 @@ alternate in one process; every repetition ends in a device synchronise and is t
 it.  Forward + backward and the forward alone (under no_grad) are timed for both.  Peak allocated memory is
 torch's, over one forward + backward, above what is allocated before it.  ``default_on`` applies the rule
 that decides the default: the fused median below the torch median and the two legs' min-max ranges apart.
+
+``--wide``: hidden dimensions above 128, which ``ResidualBlock`` sends to the kernels only up to the width set
+with ``set_fused_residual_block_width``.  The two legs are that width at 512 (the k_res_*_wide kernels) and at
+128 (the torch ops), alternating in the same way; ``ranges_apart`` says whether the forward + backward ranges of
+the two legs are disjoint and ``verdict`` which leg is faster if they are.
 """
 import argparse
 import json
@@ -52,7 +58,10 @@ def _rel(a, b):
     return float((a - b).abs().max() / b.abs().max())
 
 
-def leg(P, H, reps, warmup):
+def leg(P, H, reps, warmup, wide=False):
+    # the A/B switch and its (fused, torch ops) settings; either returns the previous setting
+    toggle, setting = ((D.set_fused_residual_block_width, {True: D.MAX_HIDDEN, False: D.MAX_FUSED_HIDDEN}) if wide
+                       else (D.set_fused_residual_blocks, {True: True, False: False}))
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(H)
     block = D.ResidualBlock(H).to(dev).train()
@@ -66,23 +75,23 @@ def leg(P, H, reps, warmup):
 
     def step(fused):
         def run():
-            previous = D.set_fused_residual_blocks(fused)
+            previous = toggle(setting[fused])
             try:
                 for p in params:
                     p.grad = None
                 block(x).backward(up)
             finally:
-                D.set_fused_residual_blocks(previous)
+                toggle(previous)
         return run
 
     def forward(fused):
         def run():
-            previous = D.set_fused_residual_blocks(fused)
+            previous = toggle(setting[fused])
             try:
                 with torch.no_grad():
                     return block(x)
             finally:
-                D.set_fused_residual_blocks(previous)
+                toggle(previous)
         return run
 
     diffs = {}
@@ -121,20 +130,28 @@ def leg(P, H, reps, warmup):
     out["speedup_forward_only"] = out["torch_ops_forward_only"]["median_ms"] / out["fused_forward_only"]["median_ms"]
     out["default_on"] = bool(f["median_ms"] < o["median_ms"] and f["max_ms"] < o["min_ms"])
     out["peak_lower"] = bool(out["fused_peak_bytes"] < out["torch_ops_peak_bytes"])
+    out["ranges_apart"] = bool(f["max_ms"] < o["min_ms"] or o["max_ms"] < f["min_ms"])
+    out["max_abs_diff_over_max_worst"] = max(diffs.values())
+    out["verdict"] = ("ranges overlap: no difference shown" if not out["ranges_apart"]
+                      else "fused faster" if f["median_ms"] < o["median_ms"] else "torch ops faster")
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--P", type=int, default=1_000_000)
-    ap.add_argument("--H", type=int, nargs="+", default=[64, 128])
+    ap.add_argument("--wide", action="store_true", help="H = 256 and 512 on the width switch, to resblock_wide_ab.json")
+    ap.add_argument("--H", type=int, nargs="+", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "resblock_ab.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.H = a.H or ([256, 512] if a.wide else [64, 128])
+    a.out = a.out or os.path.join(REPO, "profiles", "resblock_wide_ab.json" if a.wide else "resblock_ab.json")
     res = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__,
            "timing": "host perf_counter around a call that ends in torch.cuda.synchronize(); ms",
-           "legs": [leg(a.P, H, a.reps, a.warmup) for H in a.H]}
+           "switch": "set_fused_residual_block_width(512 / 128)" if a.wide else "set_fused_residual_blocks(True / False)",
+           "legs": [leg(a.P, H, a.reps, a.warmup, a.wide) for H in a.H]}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
