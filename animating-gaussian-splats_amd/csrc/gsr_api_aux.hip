@@ -551,4 +551,15 @@ int gsr_views_pack(int frames, int H, int W, const uint8_t *rgb, const uint8_t *
     return GSR_OK;
 }
 
+int gsr_frames_pack(int frames, int H, int W, const float *images, uint8_t *rgb, void *stream) {
+    if (frames < 0 || H < 0 || W < 0) return fail(GSR_ERR_ARG, "frames_pack: negative size");
+    if (frames == 0 || H == 0 || W == 0) return GSR_OK;
+    if ((long long)H * W > (1ll << 29)) return fail(GSR_ERR_UNSUPPORTED, "frames_pack: frame of %d x %d too large", H, W);
+    if (!images || !rgb) return fail(GSR_ERR_ARG, "frames_pack: null images / rgb");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "frames_pack");
+    HIP_TRY(launch_frames_pack(frames, H * W, images, rgb, s));
+    return GSR_OK;
+}
+
 }  // extern "C"

@@ -229,5 +229,7 @@ hipError_t launch_adam(const AdamTable &tab, hipStream_t s);
 // camera frames -> view tensors (gsr_io.hip)
 hipError_t launch_views_pack(int frames, int HW, const uint8_t *rgb, const uint8_t *seg, float *img, float *msk,
                              hipStream_t s);
+// rendered images -> 8-bit frames (gsr_io.hip); any alignment, any frame count
+hipError_t launch_frames_pack(int frames, int HW, const float *img, uint8_t *rgb, hipStream_t s);
 
 }  // namespace gsr

@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = (
     "gsr_posenc_ranges", "gsr_posenc_forward", "gsr_deform_in_forward", "gsr_deform_in_workspace_bytes",
     "gsr_deform_in_backward", "gsr_resblock_workspace_bytes", "gsr_resblock_forward", "gsr_resblock_backward",
     "gsr_deform_out_forward", "gsr_deform_out_workspace_bytes", "gsr_deform_out_backward",
-    "gsr_foreground_info", "gsr_rigidity_forward_state",
+    "gsr_foreground_info", "gsr_rigidity_forward_state", "gsr_frames_pack",
 )
 
 
@@ -194,7 +194,7 @@ def load_library():
     L.gsr_rigidity_backward.restype = i
     L.gsr_rigidity_backward.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
     _MISSING.clear()
-    for feature, (_, symbols) in _OPTIONAL.items():
+    for feature, (_, symbols) in (*_OPTIONAL.items(), *_OPTIONAL_EXPORT.items()):
         try:
             for name, (restype, argtypes) in symbols.items():
                 fn = getattr(L, name)
@@ -240,16 +240,22 @@ def _optional():
 # Entry points additive to ABI 21, so that a library built before them still serves everything else:
 # feature -> (its name in the error message, {symbol: (restype, argtypes)}).
 _OPTIONAL = _optional()
+# The output side's group, in a table of its own: tests/test_foreground_info.py pins _OPTIONAL's keys to
+# the training-side groups above.  Same form, same treatment by load_library and feature_library.
+_OPTIONAL_EXPORT = {"frames": ("the 8-bit frame export", {
+    "gsr_frames_pack": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3)})}
 _MISSING = {}  # feature -> why its entry points could not be bound (a stale libgsr.so)
 
 
 def feature_library(name):
     """The library, for the optional feature ``name``: "deform", "resblock" or "head" of splat_deform, or
-    "foreground" of splat_rigidity (``foreground_info``, ``calculate_rigidity_loss_and_state``).  Raises when
+    "foreground" of splat_rigidity (``foreground_info``, ``calculate_rigidity_loss_and_state``), or "frames" of
+    splat_export (``frames_to_uint8``).  Raises when
     ``libgsr.so`` predates its entry points, on first use of the feature only."""
     L = load_library()
     if name in _MISSING:
-        raise RuntimeError(f"libgsr.so at {LIB_PATH} lacks {_OPTIONAL[name][0]} ({_MISSING[name]}): "
+        what = (_OPTIONAL.get(name) or _OPTIONAL_EXPORT[name])[0]
+        raise RuntimeError(f"libgsr.so at {LIB_PATH} lacks {what} ({_MISSING[name]}): "
                            "rebuild it with `make -C animating-gaussian-splats_amd/csrc`")
     return L
 

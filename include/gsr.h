@@ -600,9 +600,19 @@ int gsr_adam_step(int ntensors, const gsr_adam_tensor *tensors, double beta1, do
 int gsr_views_pack(int frames, int H, int W, const uint8_t *rgb, const uint8_t *seg, float *images,
                    float *seg_masks, void *stream);
 
+/* ---- Rendered images -> 8-bit frames (additive to ABI 21; SURVEY.md component 9) ----
+ * Replaces the host-side composition of render_and_export_frame (train.py:534-545),
+ * (255 * np.clip(image, 0, 1)).astype(np.uint8).transpose(1, 2, 0), for `frames` images of H x W
+ * pixels at once.  `images` (frames, 3, H, W) contiguous fp32 planar, `rgb` (frames, H, W, 3) uint8
+ * interleaved; both device pointers.  Each byte: clamp to [0, 1], one float multiply by 255.0f,
+ * truncation toward zero; NaN gives 0 (numpy leaves that cast to the platform).  Any alignment and
+ * any frame count: H * W % 4 == 0 with `images` 16-byte and `rgb` 4-byte aligned takes the vector
+ * path, anything else a scalar one; more than 65535 frames go out in several launches. */
+int gsr_frames_pack(int frames, int H, int W, const float *images, uint8_t *rgb, void *stream);
+
 /* Per-phase device timing with HIP events recorded on the call's stream (off by default).
  * Phases: "preprocess", "bin_count", "bin_scan", "bin_emit", "tile_sort", "render_fwd",
- * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "knn", "rigidity_fwd", "rigidity_bwd", "foreground_info",
+ * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "frames_pack", "knn", "rigidity_fwd", "rigidity_bwd", "foreground_info",
  * "posenc_ranges", "posenc", "deform_in_fwd", "deform_in_bwd", "resblock_fwd", "resblock_bwd", "deform_out_fwd", "deform_out_bwd".  gsr_profile_read synchronises on the recorded events. */
 int gsr_profile_enable(int on);
 /* Restrict event recording to a comma-separated list of phases (NULL or "" = every phase), so a
