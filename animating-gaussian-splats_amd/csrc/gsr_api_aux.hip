@@ -147,6 +147,33 @@ int gsr_l1_ssim_backward(int planes, int H, int W, const float *img1, const floa
     return GSR_OK;
 }
 
+// ---- scores of a timestep's views (forward only) --------------------------------------------
+size_t gsr_image_scores_workspace_bytes(int views, int planes, int H, int W) {
+    if (views < 0 || planes < 0 || H < 0 || W < 0) return 0;
+    return (size_t)views * (sizeof(float) * 3 * ssim_partials(planes, H, W));
+}
+
+int gsr_image_scores(int views, int planes, int H, int W, const float *const *img1, const float *const *img2,
+                     void *workspace, float *out_scores, float *out_mean, void *stream) {
+    if (views < 0 || planes < 0 || H < 0 || W < 0) return fail(GSR_ERR_ARG, "image_scores: negative size");
+    if (views > 0 && (!img1 || !img2)) return fail(GSR_ERR_ARG, "image_scores: null image array");
+    hipStream_t s = (hipStream_t)stream;
+    if (views == 0) {  // the mean of an empty list
+        if (out_mean) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out_mean, 0x7FC00000, 1, s));
+        return GSR_OK;
+    }
+    if ((size_t)planes * H * W == 0) return fail(GSR_ERR_ARG, "image_scores: empty image (the means are undefined)");
+    if ((size_t)planes * H * W >= (size_t)1 << 31) return fail(GSR_ERR_UNSUPPORTED, "image_scores: image too large");
+    if (planes > 65535) return fail(GSR_ERR_UNSUPPORTED, "image_scores: more than 65535 planes per view");
+    for (int v = 0; v < views; ++v)
+        if (!img1[v] || !img2[v]) return fail(GSR_ERR_ARG, "image_scores: null image (view %d)", v);
+    if (!workspace || !out_scores) return fail(GSR_ERR_ARG, "image_scores: null workspace / output");
+    Phase ph(s, "image_scores");
+    HIP_TRY(launch_image_scores(views, planes, H, W, img1, img2, ssim_window(), (float *)workspace, out_scores,
+                                out_mean, s));
+    return GSR_OK;
+}
+
 // ---- rigidity loss + k-nearest neighbours ---------------------------------------------------
 int gsr_knn(int n, const float *points, int k, int *out_indices, double *out_sq_distances, void *stream) {
     if (n < 0 || k < 1) return fail(GSR_ERR_ARG, "knn: n must be >= 0 and k >= 1 (got n = %d, k = %d)", n, k);

@@ -125,6 +125,11 @@ struct SsimWindow { float w[11]; };
 size_t ssim_partials(int planes, int H, int W);
 hipError_t launch_ssim_fwd(int planes, int H, int W, const float *img1, const float *img2, const SsimWindow &w,
                            float *maps, float2 *partial, float *out_l1, float *out_ssim, hipStream_t s);
+// forward-only scoring of `views` image pairs (host arrays of device pointers); partial: views x
+// ssim_partials x 3 floats; out_scores (views, 4); out_mean may be null.  views >= 1.
+hipError_t launch_image_scores(int views, int planes, int H, int W, const float *const *img1,
+                               const float *const *img2, const SsimWindow &w, float *partial, float *out_scores,
+                               float *out_mean, hipStream_t s);
 hipError_t launch_ssim_bwd(int planes, int H, int W, const float *img1, const float *img2, const SsimWindow &w,
                            const float *maps, const float *g_l1, const float *g_ssim, float *dimg1,
                            hipStream_t s);

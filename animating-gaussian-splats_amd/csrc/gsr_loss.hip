@@ -12,6 +12,10 @@
 //                the SSIM value, three derivative maps dS/dmu1, dS/d<x^2>, dS/d<xy> + 2 dS/d<x^2> (stored
 //                for the backward) and |x - y|.  Per-wave partial sums, no atomics.
 //   k_ssim_sum   one block: fixed-order (double) sum of the block partials -> (mean |x-y|, mean S).
+//   k_ssim_eval  the forward-only form for scoring V image pairs (train.py:598-613): the same strip body
+//                (ssim_fwd_strip<false>) without the derivative maps, plus sum (x-y)^2; k_scores_sum (one
+//                block per view) and k_scores_mean turn the partials into (l1, ssim, mse, image_loss) per
+//                view and the mean image_loss.  8 B per pixel instead of 20.
 //   k_ssim_bwd   same strips: blur the three stored derivative maps (the window is symmetric, so the
 //                adjoint of the zero-padded correlation is the same correlation) and combine
 //                dL/dx = gS/N (blur(dS/dmu1) + 2 x blur(dS/d<x^2>) + y blur(dS/d<xy>)) + gL1/N sign(x-y)
@@ -35,6 +39,7 @@ constexpr int kSsRH = 32;               // output rows per wave strip (64 column
 constexpr int kSsWaves = 4;             // independent waves per 256-thread block
 constexpr int kSsRowBuf = 80;           // staged row: 64 + 2 * 5 halo columns (+ pad)
 constexpr float kSsC1 = 0.01f * 0.01f, kSsC2 = 0.03f * 0.03f;
+constexpr int kSsEvalViews = 32;        // image pairs per k_ssim_eval launch (their pointers are kernel arguments)
 
 // Strip of wave `gw`: plane, first column x0, first output row y0.
 struct SsStrip { int plane, x0, y0; };
@@ -63,23 +68,24 @@ __device__ inline void ss_load_row(const float *__restrict__ src, int H, int W, 
 // its lane's column, and keeps the last 11 rows of those sums in a register ring (slot = row mod
 // 11, resolved at compile time by unrolling 2 x 11 rows; the next two rows' loads are in flight); once 11 rows are in, the vertical window gives
 // mu1, mu2, <x^2>, <y^2>, <xy> of the output row 5 above.  No block barriers.
-__global__ __launch_bounds__(256) void k_ssim_fwd(int planes, int H, int W, int sx, int sy,
-                                                  const float *__restrict__ img1, const float *__restrict__ img2,
-                                                  SsimWindow w, float *__restrict__ maps, size_t plane_stride,
-                                                  float2 *__restrict__ partial) {
-    __shared__ float s_row[kSsWaves][2][kSsRowBuf];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gw = blockIdx.x * kSsWaves + wv;
-    if (gw >= planes * sx * sy) return;
-    const SsStrip st = ss_strip(gw, sx, sy);
+//
+// One strip's body, shared by k_ssim_fwd and k_ssim_eval.  SAVE: store the three derivative maps (the
+// training forward).  Without it (the scoring path, nothing differentiates) no map is written and
+// (x - y)^2 is summed as well; lsum and ssum take the same operations in the same order either way, so
+// they are bitwise the same.  The sums come back reduced over the wave.
+template <bool SAVE>
+__device__ __forceinline__ void ssim_fwd_strip(int planes, int H, int W, const SsStrip st, int lane,
+                                               float *ra, float *rb, const float *__restrict__ img1,
+                                               const float *__restrict__ img2, const SsimWindow &w,
+                                               float *__restrict__ maps, size_t plane_stride, float &lsum,
+                                               float &ssum, float &qsum) {
     const float *a = img1 + st.plane * plane_stride, *b = img2 + st.plane * plane_stride;
-    float *m0 = maps + st.plane * plane_stride;
-    const size_t map_stride = plane_stride * planes;  // the three maps are [3][planes][H][W]
-    float *ra = s_row[wv][0], *rb = s_row[wv][1];
+    [[maybe_unused]] float *m0 = SAVE ? maps + st.plane * plane_stride : nullptr;
+    [[maybe_unused]] const size_t map_stride = plane_stride * planes;  // the three maps are [3][planes][H][W]
     const int gx = st.x0 + lane;
     const int nin = min(kSsRH, H - st.y0) + 2 * kSsR;  // input rows this strip streams
     float h[kSsTaps][5];   // ring of horizontal sums
-    float ssum = 0.f, lsum = 0.f;
+    ssum = 0.f; lsum = 0.f; qsum = 0.f;
     // input rows prefetched 2 ahead into statically named registers (unroll by 2 x 11)
     float pf[2][4];
 #pragma unroll
@@ -106,7 +112,10 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int planes, int H, int W, int 
             for (int t = 0; t < kSsTaps; ++t) {
                 const float x = ra[lane + t], y = rb[lane + t];
                 // the centre pixel of input row i lies in output row i - 5 (L1 term)
-                if (t == kSsR && i >= kSsR && i < nin - kSsR && gx < W) lsum += fabsf(x - y);
+                if (t == kSsR && i >= kSsR && i < nin - kSsR && gx < W) {
+                    lsum += fabsf(x - y);
+                    if constexpr (!SAVE) qsum += (x - y) * (x - y);
+                }
                 h[slot][0] = fmaf(w.w[t], x, h[slot][0]);
                 h[slot][1] = fmaf(w.w[t], y, h[slot][1]);
                 h[slot][2] = fmaf(w.w[t], x * x, h[slot][2]);
@@ -122,7 +131,7 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int planes, int H, int W, int 
 #pragma unroll
                     for (int q = 0; q < 5; ++q) acc[q] = fmaf(w.w[t], h[rs][q], acc[q]);
                 }
-                const int gy = st.y0 + i - 2 * kSsR;
+                [[maybe_unused]] const int gy = st.y0 + i - 2 * kSsR;
                 if (gx < W) {
                     const float mu1 = acc[0], mu2 = acc[1];
                     const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
@@ -132,14 +141,16 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int planes, int H, int W, int 
                     const float inv = 1.f / (C * D);
                     const float S = (A * B) * inv;
                     ssum += S;
-                    // S = A B / (C D): dS/dmu1 = (2 mu2 (B - A) - 2 mu1 S (D - C)) / (C D),
-                    // dS/d<x^2> = -S / D, dS/d<xy> = 2 A / (C D); the third map is dS/d<xy> + 2 dS/d<x^2>
-                    const size_t p = (size_t)gy * W + gx;
-                    // S multiplies one rounded product, not 2 mu1 first: where mu1 = mu2, A = C and B = D the two
-                    // terms are then the same float and their difference is (1 - S) of it, not a rounding of 2 mu1 S
-                    m0[p] = 2.f * fmaf(-S, mu1 * (D - C), mu2 * (B - A)) * inv;
-                    m0[map_stride + p] = -S / D;
-                    m0[2 * map_stride + p] = 2.f * fmaf(-S, C, A) * inv;
+                    if constexpr (SAVE) {
+                        // S = A B / (C D): dS/dmu1 = (2 mu2 (B - A) - 2 mu1 S (D - C)) / (C D),
+                        // dS/d<x^2> = -S / D, dS/d<xy> = 2 A / (C D); the third map is dS/d<xy> + 2 dS/d<x^2>
+                        const size_t p = (size_t)gy * W + gx;
+                        // S multiplies one rounded product, not 2 mu1 first: where mu1 = mu2, A = C and B = D the two
+                        // terms are then the same float and their difference is (1 - S) of it, not a rounding of 2 mu1 S
+                        m0[p] = 2.f * fmaf(-S, mu1 * (D - C), mu2 * (B - A)) * inv;
+                        m0[map_stride + p] = -S / D;
+                        m0[2 * map_stride + p] = 2.f * fmaf(-S, C, A) * inv;
+                    }
                 }
             }
         }
@@ -148,8 +159,83 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int planes, int H, int W, int 
     for (int d = 32; d > 0; d >>= 1) {
         ssum += __shfl_xor(ssum, d, 64);
         lsum += __shfl_xor(lsum, d, 64);
+        if constexpr (!SAVE) qsum += __shfl_xor(qsum, d, 64);
     }
+}
+
+__global__ __launch_bounds__(256) void k_ssim_fwd(int planes, int H, int W, int sx, int sy,
+                                                  const float *__restrict__ img1, const float *__restrict__ img2,
+                                                  SsimWindow w, float *__restrict__ maps, size_t plane_stride,
+                                                  float2 *__restrict__ partial) {
+    __shared__ float s_row[kSsWaves][2][kSsRowBuf];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * kSsWaves + wv;
+    if (gw >= planes * sx * sy) return;
+    float lsum, ssum, qsum;
+    ssim_fwd_strip<true>(planes, H, W, ss_strip(gw, sx, sy), lane, s_row[wv][0], s_row[wv][1], img1, img2, w, maps,
+                         plane_stride, lsum, ssum, qsum);
     if (lane == 0) partial[gw] = make_float2(lsum, ssum);
+}
+
+// Scoring (forward only) of up to kSsEvalViews image pairs of one size: the same strips over view blockIdx.y,
+// whose two image pointers come by value in the kernel arguments (every render is a tensor of its own: no
+// stacked copy, no pointer upload).  partial: [view of this launch][wave][3] = (sum |x-y|, sum S, sum (x-y)^2).
+struct SsViewPtrs { const float *a[kSsEvalViews], *b[kSsEvalViews]; };
+__global__ __launch_bounds__(256) void k_ssim_eval(int planes, int H, int W, int sx, int sy, SsViewPtrs vp,
+                                                   SsimWindow w, size_t plane_stride, float *__restrict__ partial) {
+    __shared__ float s_row[kSsWaves][2][kSsRowBuf];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * kSsWaves + wv, nw = planes * sx * sy;
+    if (gw >= nw) return;
+    const int v = blockIdx.y;
+    float lsum, ssum, qsum;
+    ssim_fwd_strip<false>(planes, H, W, ss_strip(gw, sx, sy), lane, s_row[wv][0], s_row[wv][1], vp.a[v], vp.b[v], w,
+                          nullptr, plane_stride, lsum, ssum, qsum);
+    if (lane == 0) {
+        float *p = partial + ((size_t)v * nw + gw) * 3;
+        p[0] = lsum; p[1] = ssum; p[2] = qsum;
+    }
+}
+
+// One block per view, the sums of k_ssim_sum (same order, so l1 and ssim are bitwise its results) and the
+// squared error: out_scores[view] = (l1, ssim, mse, 0.8 l1 + 0.2 (1 - ssim)), the last in float32 in the
+// expression order of train.py:391-392.
+__global__ __launch_bounds__(256) void k_scores_sum(int nw, const float *__restrict__ partial, double inv_n,
+                                                    float *__restrict__ out_scores) {
+    __shared__ double s_l[256], s_s[256], s_q[256];
+    const float *p = partial + (size_t)blockIdx.x * nw * 3;
+    double l = 0, s = 0, q = 0;
+    for (int i = threadIdx.x; i < nw; i += 256) { l += p[3 * (size_t)i]; s += p[3 * (size_t)i + 1]; q += p[3 * (size_t)i + 2]; }
+    s_l[threadIdx.x] = l; s_s[threadIdx.x] = s; s_q[threadIdx.x] = q;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) {
+            s_l[threadIdx.x] += s_l[threadIdx.x + d]; s_s[threadIdx.x] += s_s[threadIdx.x + d];
+            s_q[threadIdx.x] += s_q[threadIdx.x + d];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float l1 = (float)(s_l[0] * inv_n), ssim = (float)(s_s[0] * inv_n);
+        float *o = out_scores + 4 * (size_t)blockIdx.x;
+        o[0] = l1; o[1] = ssim; o[2] = (float)(s_q[0] * inv_n);
+        o[3] = 0.8f * l1 + 0.2f * (1.0f - ssim);
+    }
+}
+
+// One block: the mean of the views' image_loss, summed in double in a fixed order.
+__global__ __launch_bounds__(256) void k_scores_mean(int views, const float *__restrict__ scores,
+                                                     float *__restrict__ out_mean) {
+    __shared__ double s_m[256];
+    double m = 0;
+    for (int v = threadIdx.x; v < views; v += 256) m += scores[4 * (size_t)v + 3];
+    s_m[threadIdx.x] = m;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) s_m[threadIdx.x] += s_m[threadIdx.x + d];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out_mean = (float)(s_m[0] / (double)views);
 }
 
 // One block: *out_l1 = mean |x - y|, *out_ssim = mean S over n pixels (double accumulation, fixed order).
@@ -263,6 +349,31 @@ hipError_t launch_ssim_fwd(int planes, int H, int W, const float *img1, const fl
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_ssim_sum<<<1, 256, 0, s>>>(nw, partial, 1.0 / ((double)planes * ps), out_l1, out_ssim);
+    return hipGetLastError();
+}
+
+hipError_t launch_image_scores(int views, int planes, int H, int W, const float *const *img1,
+                               const float *const *img2, const SsimWindow &w, float *partial, float *out_scores,
+                               float *out_mean, hipStream_t s) {
+    const int sx = div_up(W, 64), sy = div_up(H, kSsRH);
+    const int nw = planes * sx * sy;
+    const size_t ps = (size_t)H * W;
+    for (int v0 = 0; v0 < views; v0 += kSsEvalViews) {  // kSsEvalViews pointer pairs per launch
+        const int n = min(kSsEvalViews, views - v0);
+        SsViewPtrs vp;
+        for (int k = 0; k < kSsEvalViews; ++k) {
+            vp.a[k] = k < n ? img1[v0 + k] : nullptr;
+            vp.b[k] = k < n ? img2[v0 + k] : nullptr;
+        }
+        k_ssim_eval<<<dim3(div_up(nw, kSsWaves), n), 64 * kSsWaves, 0, s>>>(planes, H, W, sx, sy, vp, w, ps,
+                                                                            partial + (size_t)v0 * nw * 3);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    k_scores_sum<<<views, 256, 0, s>>>(nw, partial, 1.0 / ((double)planes * ps), out_scores);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !out_mean) return e;
+    k_scores_mean<<<1, 256, 0, s>>>(views, out_scores, out_mean);
     return hipGetLastError();
 }
 

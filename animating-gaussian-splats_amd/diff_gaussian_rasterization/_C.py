@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "gsr_deform_in_backward", "gsr_resblock_workspace_bytes", "gsr_resblock_forward", "gsr_resblock_backward",
     "gsr_deform_out_forward", "gsr_deform_out_workspace_bytes", "gsr_deform_out_backward",
     "gsr_foreground_info", "gsr_rigidity_forward_state", "gsr_frames_pack",
+    "gsr_image_scores_workspace_bytes", "gsr_image_scores",
 )
 
 
@@ -243,14 +244,17 @@ _OPTIONAL = _optional()
 # The output side's group, in a table of its own: tests/test_foreground_info.py pins _OPTIONAL's keys to
 # the training-side groups above.  Same form, same treatment by load_library and feature_library.
 _OPTIONAL_EXPORT = {"frames": ("the 8-bit frame export", {
-    "gsr_frames_pack": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3)})}
+    "gsr_frames_pack": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3)}),
+                    "scores": ("the forward-only image scores", {
+    "gsr_image_scores_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "gsr_image_scores": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p] * 6)})}
 _MISSING = {}  # feature -> why its entry points could not be bound (a stale libgsr.so)
 
 
 def feature_library(name):
     """The library, for the optional feature ``name``: "deform", "resblock" or "head" of splat_deform, or
     "foreground" of splat_rigidity (``foreground_info``, ``calculate_rigidity_loss_and_state``), or "frames" of
-    splat_export (``frames_to_uint8``).  Raises when
+    splat_export (``frames_to_uint8``), or "scores" of splat_loss (``image_scores``).  Raises when
     ``libgsr.so`` predates its entry points, on first use of the feature only."""
     L = load_library()
     if name in _MISSING:

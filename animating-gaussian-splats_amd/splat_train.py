@@ -18,6 +18,8 @@ optimizer.step(); zero_grad(set_to_none)    :246-247    splat_adam.FusedAdam (on
 ``train_step_loss`` is the loss of one train.py step (train.py:395-418): the views' renders and image
 losses as above plus the rigidity term of ``splat_rigidity``, evaluated once per step.
 ``advance_timestep`` hands a finished timestep's cloud and rigidity state to the next (train.py:251-266).
+``evaluate_views`` is the comparison half of an inference timestep (train.py:598-613) and ``ScoreLog`` takes
+its numbers to the host without a synchronisation.
 
 ``View`` restates shared.py:13-18.  The image-render ``means2D`` is a leaf that receives the same
 screen-space (NDC) gradient the reference reads through ``retain_grad`` (densify.py:119).
@@ -33,7 +35,8 @@ import splat_loss
 import splat_rigidity
 from diff_gaussian_rasterization import GaussianRasterizationSettings, rasterize_parameters
 
-__all__ = ["View", "densify_iteration", "create_densification_variables", "train_step_loss", "advance_timestep"]
+__all__ = ["View", "densify_iteration", "create_densification_variables", "train_step_loss", "advance_timestep",
+           "evaluate_views", "ScoreLog"]
 
 
 @dataclass
@@ -105,6 +108,110 @@ def train_step_loss(params, views, neighbor_info, foreground_info, next_foregrou
     if next_foreground_info:
         return total, l1_sum, ssim_sum, rigidity_sum, state
     return total, l1_sum, ssim_sum, rigidity_sum
+
+
+def evaluate_views(params, views):
+    """train.py:598-613 without the loading and the logging: every view of a timestep rendered under
+    ``no_grad`` (``rasterize_parameters``) and all of them compared with their images in one forward-only
+    pass.  Returns ``splat_loss.image_scores``' result: per view ``l1``, ``ssim``, ``mse``, ``psnr`` and
+    ``image_loss = 0.8 l1 + 0.2 (1 - ssim)``, and ``mean_image_loss``, the reference's ``mean-image-loss``.
+    Device tensors; nothing is synchronised (``ScoreLog`` takes them to the host)."""
+    if not views:
+        raise ValueError("evaluate_views: no views")
+    with torch.no_grad():
+        renders = [rasterize_parameters(params, view.render_settings)[0] for view in views]
+    return splat_loss.image_scores(renders, [view.image for view in views])
+
+
+class ScoreLog:
+    """The metric's way to the host without a synchronisation: a ring of ``depth`` pinned host slots,
+    modelled on ``splat_export.FrameWriter``.
+
+    ``put(step, scores)``: ``scores`` is ``image_scores``' result or one tensor; its values are packed and
+    copied into the next slot asynchronously, with an event behind the copy.  ``drain()`` returns the
+    ``(step, values)`` pairs whose copies have landed, in the order they were put, without blocking;
+    ``values`` is an ``ImageScores`` of host tensors, or a host tensor.  A full ring makes ``put`` wait for
+    its oldest slot, whose pair is kept for the next ``drain``.  ``close()`` waits for the rest and returns it."""
+
+    def __init__(self, depth: int = 8):
+        if depth < 1:
+            raise ValueError(f"ScoreLog: got depth={depth}, expected at least 1")
+        self.depth = depth
+        self._slots = [None] * depth   # (step, staging view, event, views V or None) of a copy in flight
+        self._staging = [None] * depth
+        self._head = self._count = 0   # oldest slot in flight, slots in flight
+        self._done = []
+        self._closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __len__(self):
+        """Pairs not yet returned by ``drain``."""
+        return self._count + len(self._done)
+
+    def _finish_oldest(self):
+        step, staged, event, V = self._slots[self._head]
+        if event is not None:
+            event.synchronize()
+        host = staged.clone()  # the slot is reused
+        if V is None:
+            values = host
+        else:
+            rows = host[:5 * V].view(5, V)
+            values = splat_loss.ImageScores(rows[0], rows[1], rows[2], rows[3], rows[4], host[5 * V])
+        self._done.append((step, values))
+        self._slots[self._head] = None
+        self._head = (self._head + 1) % self.depth
+        self._count -= 1
+
+    def put(self, step, scores):
+        if self._closed:
+            raise RuntimeError("ScoreLog: put after close()")
+        if isinstance(scores, splat_loss.ImageScores):
+            V = scores.l1.numel()
+            packed = torch.cat([torch.stack(scores[:5]).reshape(-1), scores.mean_image_loss.reshape(1)])
+        elif isinstance(scores, torch.Tensor):
+            V, packed = None, scores.detach()
+        else:
+            raise TypeError(f"ScoreLog.put: got {type(scores).__name__}, expected image_scores' result or a tensor")
+        if self._count == self.depth:
+            self._finish_oldest()  # blocks on the oldest copy; its pair waits in _done
+        k = (self._head + self._count) % self.depth
+        n = packed.numel()
+        st = self._staging[k]
+        if st is None or st.numel() < n or st.dtype != packed.dtype:
+            st = self._staging[k] = torch.empty(max(n, 1), dtype=packed.dtype, pin_memory=torch.cuda.is_available())
+        staged = st[:n].view(packed.shape)
+        event = None
+        if packed.is_cuda:
+            staged.copy_(packed, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(packed.device))
+        else:
+            staged.copy_(packed)
+        self._slots[k] = (step, staged, event, V)
+        self._count += 1
+
+    def drain(self):
+        while self._count:
+            event = self._slots[self._head][2]
+            if event is not None and not event.query():
+                break  # later copies are behind it on the stream
+            self._finish_oldest()
+        done, self._done = self._done, []
+        return done
+
+    def close(self):
+        self._closed = True
+        while self._count:
+            self._finish_oldest()
+        done, self._done = self._done, []
+        return done
 
 
 def advance_timestep(updated_params, neighbor_info, foreground_info=None):

@@ -371,6 +371,22 @@ int gsr_l1_ssim_backward(int planes, int height, int width, const float *img1, c
                          const void *scratch, const float *dL_dl1, const float *dL_dssim,
                          float *dL_dimg1, void *stream);
 
+/* ---- Scores of a timestep's views (additive to ABI 21; SURVEY.md component 9) -------------------
+ * The comparison half of the inference loop, train.py:598-613: `views` image pairs of one size, each
+ * `planes_per_view` contiguous fp32 planes of height x width, scored forward-only (no derivative maps
+ * are written).  img1 / img2 are HOST arrays of `views` device pointers (every render is a tensor of
+ * its own; the pointers travel in the kernel arguments, 32 pairs per launch).  out_scores (views, 4),
+ * device: l1 = mean |img1 - img2|, ssim = calc_ssim, mse = mean (img1 - img2)^2 and image_loss =
+ * 0.8 l1 + 0.2 (1 - ssim) in float32 (train.py:391-392); l1 and ssim are bitwise what
+ * gsr_l1_ssim_forward gives for that pair alone.  out_mean_image_loss (device scalar, may be NULL):
+ * the mean of the views' image_loss, summed in double in a fixed order.  The workspace holds
+ * views x planes_per_view x ceil(width / 64) x ceil(height / 32) partial sums of 12 bytes.  No
+ * atomics: results are bitwise repeatable.  views = 0 launches nothing; the mean is then NaN. */
+size_t gsr_image_scores_workspace_bytes(int views, int planes_per_view, int height, int width);
+int gsr_image_scores(int views, int planes_per_view, int height, int width, const float *const *img1,
+                     const float *const *img2, void *workspace, float *out_scores,
+                     float *out_mean_image_loss, void *stream);
+
 /* ---- Rigidity loss and exact k-nearest neighbours (additive to ABI 21) ------------------------
  * gsr_knn: the k nearest OTHER points of each of n fp32 points (n, 3), the counterpart of
  * compute_knn_indices_and_squared_distances (shared.py:45-61).  Squared distances are evaluated in
@@ -612,7 +628,7 @@ int gsr_frames_pack(int frames, int H, int W, const float *images, uint8_t *rgb,
 
 /* Per-phase device timing with HIP events recorded on the call's stream (off by default).
  * Phases: "preprocess", "bin_count", "bin_scan", "bin_emit", "tile_sort", "render_fwd",
- * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "densify_plan", "densify_apply", "adam", "views_pack", "frames_pack", "knn", "rigidity_fwd", "rigidity_bwd", "foreground_info",
+ * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "image_scores", "densify_plan", "densify_apply", "adam", "views_pack", "frames_pack", "knn", "rigidity_fwd", "rigidity_bwd", "foreground_info",
  * "posenc_ranges", "posenc", "deform_in_fwd", "deform_in_bwd", "resblock_fwd", "resblock_bwd", "deform_out_fwd", "deform_out_bwd".  gsr_profile_read synchronises on the recorded events. */
 int gsr_profile_enable(int on);
 /* Restrict event recording to a comma-separated list of phases (NULL or "" = every phase), so a
