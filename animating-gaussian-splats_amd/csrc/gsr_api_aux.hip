@@ -1,6 +1,7 @@
 // gsr_api_aux.hip -- C ABI of libgsr (declared in include/gsr.h): the entry points beside the
 // rasterizer -- fused L1 + SSIM, k-nearest neighbours and the rigidity loss, the deformation network's
-// input layer, residual blocks and output head, densification, fused Adam and the camera-frame packing.
+// input layer, residual blocks and output head, densification, fused Adam with the gradient norm and the
+// camera-frame packing.
 // Argument validation and workspace carving; the kernels are in gsr_loss.hip, gsr_rigidity.hip, gsr_deform.hip,
 // gsr_resblock.hip, gsr_head.hip, gsr_densify.hip, gsr_adam.hip and gsr_io.hip.
 #include <hip/hip_runtime.h>
@@ -108,6 +109,78 @@ int dens_args(const gsr_densify_settings *st, DensArgs &a) {
     a.opacity_logits = st->opacity_logits; a.rotations = st->rotation_quaternions;
     return GSR_OK;
 }
+
+// fused Adam: the tensor list's checks (before anything is launched), and the launch table
+constexpr long long kAdamMaxNumel = (1ll << 30) * kAdamPerBlock;  // 2^30 blocks, the most one launch takes
+int check_adam(int ntensors, const gsr_adam_tensor *tensors) {
+    if (ntensors < 0 || (ntensors > 0 && !tensors)) return fail(GSR_ERR_ARG, "adam: bad tensor list");
+    for (int k = 0; k < ntensors; ++k) {
+        const gsr_adam_tensor &a = tensors[k];
+        if (a.numel < 0) return fail(GSR_ERR_ARG, "adam: tensor %d: negative numel", k);
+        if (a.numel > 0 && (!a.param || !a.grad || !a.exp_avg || !a.exp_avg_sq))
+            return fail(GSR_ERR_ARG, "adam: tensor %d: null pointer", k);
+        if (a.numel > 0 && !(a.step >= 1.0)) return fail(GSR_ERR_ARG, "adam: tensor %d: step must be >= 1", k);
+        if (a.numel > kAdamMaxNumel) return fail(GSR_ERR_UNSUPPORTED, "adam: tensor %d too large", k);
+    }
+    return GSR_OK;
+}
+void adam_table_reset(AdamTable &tab, double beta1, double beta2, double eps) {
+    memset(&tab, 0, sizeof(tab));
+    tab.w1 = (float)(1.0 - beta1);
+    tab.b2 = (float)beta2;
+    tab.omb2 = (float)(1.0 - beta2);
+    tab.eps = (float)eps;
+}
+// the table's next entry: tensor `a`, whose first block is the table's block `nb`
+void adam_table_add(AdamTable &tab, const gsr_adam_tensor &a, double beta1, double beta2, int nb) {
+    const double bc1 = 1.0 - std::pow(beta1, a.step), bc2 = 1.0 - std::pow(beta2, a.step);
+    AdamTensor &t = tab.t[tab.n];
+    t.param = a.param; t.grad = a.grad; t.exp_avg = a.exp_avg; t.exp_avg_sq = a.exp_avg_sq;
+    t.n = a.numel;
+    t.step_size = (float)((a.lr / bc1) * -1.0);
+    t.bc2_sqrt = (float)std::pow(bc2, 0.5);
+    const uintptr_t al = (uintptr_t)a.param | (uintptr_t)a.grad | (uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq;
+    t.vec4 = (al & 15) == 0;
+    tab.block_start[tab.n] = nb;
+    ++tab.n;
+}
+
+// The gradient norm's side of a call: the workspace (doubles: the total, one sum per slot, one partial per
+// block of the call) and the table k_norm_final gets after each reducing launch.  A table takes up to
+// kAdamMaxTensors tensors of the list, the empty ones included (they own a slot and no partials).
+struct NormRun {
+    hipStream_t s;
+    double *total, *sums, *partials;
+    float *out_sq, *out_norm;
+    int last;
+    NormFinal f;
+    long long base = 0;  // blocks of the call's earlier tables
+    int nb = 0;          // blocks of this table so far
+    NormRun(hipStream_t s_, void *ws, int nslots, int last_, float *out_sq_, float *out_norm_)
+        : s(s_), total((double *)ws), sums((double *)ws + 1), partials((double *)ws + 1 + nslots), out_sq(out_sq_),
+          out_norm(out_norm_), last(last_) {
+        memset(&f, 0, sizeof(f));
+        f.nslots = nslots;
+    }
+    bool full(int blocks) const { return f.n == kAdamMaxTensors || nb + (long long)blocks > (1ll << 30); }
+    double *table_partials() const { return partials + base; }
+    void add(int slot, int blocks) {
+        f.slot[f.n] = slot;
+        f.part_start[f.n] = nb;
+        nb += blocks;
+        f.part_start[++f.n] = nb;
+    }
+    hipError_t flush(bool end_of_call) {
+        f.last = end_of_call && last;
+        hipError_t e = launch_norm_final(f, table_partials(), sums, total, out_sq, out_norm, s);
+        base += nb;
+        nb = 0;
+        const int nslots = f.nslots;
+        memset(&f, 0, sizeof(f));
+        f.nslots = nslots;
+        return e;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -507,26 +580,12 @@ int gsr_densify_apply(const gsr_densify_settings *st, const void *workspace, con
 
 int gsr_adam_step(int ntensors, const gsr_adam_tensor *tensors, double beta1, double beta2, double eps,
                   void *stream) {
-    if (ntensors < 0 || (ntensors > 0 && !tensors)) return fail(GSR_ERR_ARG, "adam: bad tensor list");
+    int rc = check_adam(ntensors, tensors);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    for (int k = 0; k < ntensors; ++k) {  // validate everything before launching anything
-        const gsr_adam_tensor &a = tensors[k];
-        if (a.numel < 0) return fail(GSR_ERR_ARG, "adam: tensor %d: negative numel", k);
-        if (a.numel > 0 && (!a.param || !a.grad || !a.exp_avg || !a.exp_avg_sq))
-            return fail(GSR_ERR_ARG, "adam: tensor %d: null pointer", k);
-        if (a.numel > 0 && !(a.step >= 1.0)) return fail(GSR_ERR_ARG, "adam: tensor %d: step must be >= 1", k);
-        if (adam_blocks(a.numel) > (1 << 30)) return fail(GSR_ERR_UNSUPPORTED, "adam: tensor %d too large", k);
-    }
     Phase ph(s, "adam");
     AdamTable tab;
-    auto reset = [&]() {
-        memset(&tab, 0, sizeof(tab));
-        tab.w1 = (float)(1.0 - beta1);
-        tab.b2 = (float)beta2;
-        tab.omb2 = (float)(1.0 - beta2);
-        tab.eps = (float)eps;
-    };
-    reset();
+    adam_table_reset(tab, beta1, beta2, eps);
     int nb = 0;
     for (int k = 0; k < ntensors; ++k) {
         const gsr_adam_tensor &a = tensors[k];
@@ -535,25 +594,104 @@ int gsr_adam_step(int ntensors, const gsr_adam_tensor *tensors, double beta1, do
         if (tab.n == kAdamMaxTensors || nb + (long long)b > (1ll << 30)) {  // table full: launch it
             tab.block_start[tab.n] = nb;
             HIP_TRY(launch_adam(tab, s));
-            reset();
+            adam_table_reset(tab, beta1, beta2, eps);
             nb = 0;
         }
-        const double bc1 = 1.0 - std::pow(beta1, a.step), bc2 = 1.0 - std::pow(beta2, a.step);
-        AdamTensor &t = tab.t[tab.n];
-        t.param = a.param; t.grad = a.grad; t.exp_avg = a.exp_avg; t.exp_avg_sq = a.exp_avg_sq;
-        t.n = a.numel;
-        t.step_size = (float)((a.lr / bc1) * -1.0);
-        t.bc2_sqrt = (float)std::pow(bc2, 0.5);
-        const uintptr_t al = (uintptr_t)a.param | (uintptr_t)a.grad | (uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq;
-        t.vec4 = (al & 15) == 0;
-        tab.block_start[tab.n] = nb;
+        adam_table_add(tab, a, beta1, beta2, nb);
         nb += b;
-        ++tab.n;
     }
     if (tab.n) {
         tab.block_start[tab.n] = nb;
         HIP_TRY(launch_adam(tab, s));
     }
+    return GSR_OK;
+}
+
+// ---- gradient norm --------------------------------------------------------------------------------
+size_t gsr_grad_norm_workspace_bytes(int ntensors, const long long *numels) {
+    if (ntensors < 0 || (ntensors > 0 && !numels)) return 0;
+    size_t doubles = 1 + (size_t)ntensors;
+    for (int k = 0; k < ntensors; ++k) {
+        if (numels[k] < 0) return 0;
+        doubles += (size_t)(numels[k] / kAdamPerBlock) + (numels[k] % kAdamPerBlock != 0);
+    }
+    return sizeof(double) * doubles;
+}
+
+int gsr_grad_norm(int ntensors, const gsr_grad_tensor *tensors, void *workspace, float *out_sqnorms,
+                  float *out_norm, void *stream) {
+    if (ntensors < 0 || (ntensors > 0 && !tensors)) return fail(GSR_ERR_ARG, "grad_norm: bad tensor list");
+    for (int k = 0; k < ntensors; ++k) {  // validate everything before launching anything
+        if (tensors[k].numel < 0) return fail(GSR_ERR_ARG, "grad_norm: tensor %d: negative numel", k);
+        if (tensors[k].numel > 0 && !tensors[k].grad) return fail(GSR_ERR_ARG, "grad_norm: tensor %d: null gradient", k);
+        if (tensors[k].numel > kAdamMaxNumel) return fail(GSR_ERR_UNSUPPORTED, "grad_norm: tensor %d too large", k);
+    }
+    if (!workspace || !out_norm) return fail(GSR_ERR_ARG, "grad_norm: null workspace / out_norm");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "grad_norm");
+    if (ntensors == 0) {  // the norm of nothing
+        HIP_TRY(hipMemsetAsync(out_norm, 0, sizeof(float), s));
+        return GSR_OK;
+    }
+    NormRun run(s, workspace, ntensors, 1, out_sqnorms, out_norm);
+    NormTable tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int k = 0; k < ntensors; ++k) {
+        const gsr_grad_tensor &a = tensors[k];
+        const int b = adam_blocks(a.numel);
+        if (run.full(b)) {  // table full: reduce it, sum its tensors
+            tab.block_start[tab.n] = run.nb;
+            HIP_TRY(launch_grad_sumsq(tab, run.table_partials(), s));
+            HIP_TRY(run.flush(false));
+            memset(&tab, 0, sizeof(tab));
+        }
+        if (a.numel > 0) {
+            tab.t[tab.n] = NormTensor{a.grad, a.numel, ((uintptr_t)a.grad & 15) == 0};
+            tab.block_start[tab.n++] = run.nb;
+        }
+        run.add(k, b);
+    }
+    tab.block_start[tab.n] = run.nb;
+    HIP_TRY(launch_grad_sumsq(tab, run.table_partials(), s));
+    HIP_TRY(run.flush(true));
+    return GSR_OK;
+}
+
+int gsr_adam_step_norm(int ntensors, const gsr_adam_tensor *tensors, double beta1, double beta2, double eps,
+                       void *workspace, const int *slots, int nslots, int last, float *out_sqnorms,
+                       float *out_norm, void *stream) {
+    int rc = check_adam(ntensors, tensors);
+    if (rc) return rc;
+    if (nslots < 0 || (!slots && ntensors > nslots))
+        return fail(GSR_ERR_ARG, "adam_norm: %d tensors but %d slots", ntensors, nslots);
+    for (int k = 0; slots && k < ntensors; ++k)
+        if (slots[k] < 0 || slots[k] >= nslots)
+            return fail(GSR_ERR_ARG, "adam_norm: tensor %d: slot %d outside [0, %d)", k, slots[k], nslots);
+    if (!workspace || !out_norm) return fail(GSR_ERR_ARG, "adam_norm: null workspace / out_norm");
+    hipStream_t s = (hipStream_t)stream;
+    Phase ph(s, "adam");
+    if (nslots == 0) {  // the norm of nothing
+        if (last) HIP_TRY(hipMemsetAsync(out_norm, 0, sizeof(float), s));
+        return GSR_OK;
+    }
+    NormRun run(s, workspace, nslots, last, out_sqnorms, out_norm);
+    AdamTable tab;
+    adam_table_reset(tab, beta1, beta2, eps);
+    for (int k = 0; k < ntensors; ++k) {
+        const gsr_adam_tensor &a = tensors[k];
+        const int b = adam_blocks(a.numel);
+        if (run.full(b)) {  // table full: update it, sum its tensors
+            tab.block_start[tab.n] = run.nb;
+            HIP_TRY(launch_adam_norm(tab, run.table_partials(), s));
+            HIP_TRY(run.flush(false));
+            adam_table_reset(tab, beta1, beta2, eps);
+        }
+        if (a.numel > 0) adam_table_add(tab, a, beta1, beta2, run.nb);
+        run.add(slots ? slots[k] : k, b);
+    }
+    tab.block_start[tab.n] = run.nb;
+    HIP_TRY(launch_adam_norm(tab, run.table_partials(), s));
+    if (run.f.n || last) HIP_TRY(run.flush(true));
     return GSR_OK;
 }
 

@@ -223,6 +223,8 @@ struct AdamTensor {
     long long n; float step_size, bc2_sqrt; int vec4;
 };
 constexpr int kAdamMaxTensors = 16;
+constexpr int kAdamThreads = 256;
+constexpr int kAdamPerBlock = kAdamThreads * 4;  // elements per block: 4 per thread
 struct AdamTable {
     int n; float w1, b2, omb2, eps;
     AdamTensor t[kAdamMaxTensors];
@@ -230,6 +232,27 @@ struct AdamTable {
 };
 int adam_blocks(long long n);
 hipError_t launch_adam(const AdamTable &tab, hipStream_t s);
+// gradient norm (gsr_adam.hip): one double per block of kAdamPerBlock elements at partials[block in
+// the table], by the update itself (launch_adam_norm) or by a reduction-only pass (launch_grad_sumsq);
+// launch_norm_final sums each table entry's partials [part_start[k], part_start[k + 1]) into
+// tensor_sums[slot[k]] (and out_sqnorms[slot[k]] when given) and, on the call's last table, the slots
+// 0 .. nslots-1 in order into *total and sqrt(*total) into *out_norm.  An entry may have no partials (an
+// empty tensor: its sum is 0).
+struct NormTensor { const float *grad; long long n; int vec4; };
+struct NormTable {
+    int n;
+    NormTensor t[kAdamMaxTensors];
+    int block_start[kAdamMaxTensors + 1];
+};
+struct NormFinal {
+    int n, nslots, last;
+    int slot[kAdamMaxTensors];
+    int part_start[kAdamMaxTensors + 1];
+};
+hipError_t launch_adam_norm(const AdamTable &tab, double *partials, hipStream_t s);
+hipError_t launch_grad_sumsq(const NormTable &tab, double *partials, hipStream_t s);
+hipError_t launch_norm_final(const NormFinal &f, const double *partials, double *tensor_sums, double *total,
+                             float *out_sqnorms, float *out_norm, hipStream_t s);
 
 // camera frames -> view tensors (gsr_io.hip)
 hipError_t launch_views_pack(int frames, int HW, const uint8_t *rgb, const uint8_t *seg, float *img, float *msk,

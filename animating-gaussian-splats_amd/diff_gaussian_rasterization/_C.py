@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "gsr_deform_out_forward", "gsr_deform_out_workspace_bytes", "gsr_deform_out_backward",
     "gsr_foreground_info", "gsr_rigidity_forward_state", "gsr_frames_pack",
     "gsr_image_scores_workspace_bytes", "gsr_image_scores",
+    "gsr_grad_norm_workspace_bytes", "gsr_grad_norm", "gsr_adam_step_norm",
 )
 
 
@@ -247,14 +248,22 @@ _OPTIONAL_EXPORT = {"frames": ("the 8-bit frame export", {
     "gsr_frames_pack": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3)}),
                     "scores": ("the forward-only image scores", {
     "gsr_image_scores_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
-    "gsr_image_scores": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p] * 6)})}
+    "gsr_image_scores": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p] * 6)}),
+                    # (the tensor lists go in as void pointers: splat_adam owns their ctypes structures)
+                    "gradnorm": ("the gradient norm", {
+    "gsr_grad_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
+    "gsr_grad_norm": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5),
+    "gsr_adam_step_norm": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p] + [ctypes.c_double] * 3 +
+                           [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int] +
+                           [ctypes.c_void_p] * 3)})}
 _MISSING = {}  # feature -> why its entry points could not be bound (a stale libgsr.so)
 
 
 def feature_library(name):
     """The library, for the optional feature ``name``: "deform", "resblock" or "head" of splat_deform, or
     "foreground" of splat_rigidity (``foreground_info``, ``calculate_rigidity_loss_and_state``), or "frames" of
-    splat_export (``frames_to_uint8``), or "scores" of splat_loss (``image_scores``).  Raises when
+    splat_export (``frames_to_uint8``), or "scores" of splat_loss (``image_scores``), or "gradnorm" of
+    splat_adam (``gradient_norm``, ``FusedAdam.step(grad_norm=True)``).  Raises when
     ``libgsr.so`` predates its entry points, on first use of the feature only."""
     L = load_library()
     if name in _MISSING:

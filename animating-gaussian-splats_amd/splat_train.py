@@ -19,7 +19,9 @@ optimizer.step(); zero_grad(set_to_none)    :246-247    splat_adam.FusedAdam (on
 losses as above plus the rigidity term of ``splat_rigidity``, evaluated once per step.
 ``advance_timestep`` hands a finished timestep's cloud and rigidity state to the next (train.py:251-266).
 ``evaluate_views`` is the comparison half of an inference timestep (train.py:598-613) and ``ScoreLog`` takes
-its numbers to the host without a synchronisation.
+its numbers to the host without a synchronisation.  ``step_metrics`` packs what a training step logs
+(train.py:419-428, :769-772) for the same ``ScoreLog``; the gradient norm in it comes from
+``splat_adam.gradient_norm`` or ``FusedAdam.step(grad_norm=True)``.
 
 ``View`` restates shared.py:13-18.  The image-render ``means2D`` is a leaf that receives the same
 screen-space (NDC) gradient the reference reads through ``retain_grad`` (densify.py:119).
@@ -36,7 +38,7 @@ import splat_rigidity
 from diff_gaussian_rasterization import GaussianRasterizationSettings, rasterize_parameters
 
 __all__ = ["View", "densify_iteration", "create_densification_variables", "train_step_loss", "advance_timestep",
-           "evaluate_views", "ScoreLog"]
+           "evaluate_views", "ScoreLog", "step_metrics", "STEP_METRIC_NAMES"]
 
 
 @dataclass
@@ -108,6 +110,23 @@ def train_step_loss(params, views, neighbor_info, foreground_info, next_foregrou
     if next_foreground_info:
         return total, l1_sum, ssim_sum, rigidity_sum, state
     return total, l1_sum, ssim_sum, rigidity_sum
+
+
+STEP_METRIC_NAMES = ("train-loss/total", "train-loss/l1", "train-loss/ssim", "train-loss/image",
+                     "train-loss/rigidity", "gradient-norm")
+
+
+def step_metrics(losses, gradient_norm):
+    """What a train.py step logs (train.py:419-428 and :769-772) as ONE float32 tensor of six values in
+    ``STEP_METRIC_NAMES`` order, for ``ScoreLog.put(step, ...)``: the reference reads each of them with its
+    own ``.item()``.  ``losses`` is ``train_step_loss``'s tuple, ``gradient_norm`` the scalar of
+    ``splat_adam.gradient_norm`` or ``FusedAdam.step(grad_norm=True)``.  ``image`` is
+    ``0.8 l1_sum + 0.2 ssim_sum`` in float32 (train.py:391-392).  Torch operations only; nothing is
+    synchronised."""
+    total, l1_sum, ssim_sum, rigidity_sum = (x.detach().float() for x in losses[:4])
+    image = 0.8 * l1_sum + 0.2 * ssim_sum
+    return torch.stack([total, l1_sum, ssim_sum, image, rigidity_sum,
+                        gradient_norm.detach().float().to(total.device)]).reshape(6)
 
 
 def evaluate_views(params, views):

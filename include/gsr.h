@@ -607,6 +607,48 @@ typedef struct gsr_adam_tensor {
 int gsr_adam_step(int ntensors, const gsr_adam_tensor *tensors, double beta1, double beta2, double eps,
                   void *stream);
 
+/* ---- Gradient norm of a list of tensors, alone or inside the Adam step (additive to ABI 21) --------
+ * Replaces calculate_gradient_norm (train.py:432-443: one .norm(2).pow(2) and one blocking host read per
+ * parameter) without any host synchronisation or host-to-device copy.
+ *
+ * Value: out_norm = sqrt(sum_t sum_i g_ti^2).  Every element is converted to double and squared (exact),
+ * the squares are summed in double -- per block of 1024 elements, per tensor, then over the tensors --
+ * and each result is rounded once to float32: out_sqnorms[slot] = the tensor's sum of squares (may be NULL),
+ * out_norm = the square root of the total.  Both are device pointers.
+ * NaN: a NaN element makes its own tensor's out_sqnorms entry and out_norm NaN; the other tensors'
+ * entries are unaffected.
+ * Large gradients: the sums do not overflow where float32 would.  A tensor of 1000 x 1e20 has a finite
+ * out_norm (3.16e21) although its squared norm (1e43) is inf as a float32 -- out_sqnorms holds inf there
+ * -- whereas the reference's float32 expression, norm(2).pow(2), gives inf for the norm too.  This
+ * difference is deliberate.
+ * Repeatability: all orders of summation are fixed (tensor sums are added in slot order) and no atomics are
+ * used, so results are bitwise repeatable, and gsr_adam_step_norm gives bitwise what gsr_grad_norm gives
+ * for the same gradients in the same slots, whatever the tensors' alignment and however they are spread
+ * over calls.
+ *
+ * Workspace (gsr_grad_norm_workspace_bytes over the element counts of every tensor that gets a slot;
+ * 8-byte aligned): one double for the total, one per slot and one per block of 1024 elements.
+ *
+ * gsr_grad_norm: tensor k owns slot k.  At most two launches per 16 tensors; no tensors at all only clear
+ * out_norm.  Empty tensors (numel 0, grad may be NULL) have a squared norm of 0.
+ *
+ * gsr_adam_step_norm: gsr_adam_step (same arguments, same update bit for bit) whose launches also reduce the
+ * gradients they read.  Tensor k owns slot slots[k] of `nslots` (slots == NULL: slot k).  Several calls
+ * -- one per (betas, eps) configuration -- form one norm by sharing the workspace and the outputs on one
+ * stream, with disjoint slots that together cover 0 .. nslots-1; the call with `last` != 0 comes last and
+ * writes out_norm (and the double total, workspace[0]) from all slots. */
+typedef struct gsr_grad_tensor {
+    const float *grad;
+    long long numel;
+} gsr_grad_tensor;
+
+size_t gsr_grad_norm_workspace_bytes(int ntensors, const long long *numels);
+int gsr_grad_norm(int ntensors, const gsr_grad_tensor *tensors, void *workspace, float *out_sqnorms,
+                  float *out_norm, void *stream);
+int gsr_adam_step_norm(int ntensors, const gsr_adam_tensor *tensors, double beta1, double beta2, double eps,
+                       void *workspace, const int *slots, int nslots, int last, float *out_sqnorms,
+                       float *out_norm, void *stream);
+
 /* ---- Camera frames of one timestep -> the reference's view tensors (ABI >= 7) ----
  * Replaces the per-view tensor formatting of load_timestep_views (shared.py:127-171) for `frames`
  * frames of H x W pixels at once.  Inputs are device pointers to the decoded 8-bit data: `rgb`
@@ -628,7 +670,7 @@ int gsr_frames_pack(int frames, int H, int W, const float *images, uint8_t *rgb,
 
 /* Per-phase device timing with HIP events recorded on the call's stream (off by default).
  * Phases: "preprocess", "bin_count", "bin_scan", "bin_emit", "tile_sort", "render_fwd",
- * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "image_scores", "densify_plan", "densify_apply", "adam", "views_pack", "frames_pack", "knn", "rigidity_fwd", "rigidity_bwd", "foreground_info",
+ * "bwd_items", "render_bwd", "sum_records", "gauss_bwd", "ssim_fwd", "ssim_bwd", "image_scores", "densify_plan", "densify_apply", "adam", "grad_norm", "views_pack", "frames_pack", "knn", "rigidity_fwd", "rigidity_bwd", "foreground_info",
  * "posenc_ranges", "posenc", "deform_in_fwd", "deform_in_bwd", "resblock_fwd", "resblock_bwd", "deform_out_fwd", "deform_out_bwd".  gsr_profile_read synchronises on the recorded events. */
 int gsr_profile_enable(int on);
 /* Restrict event recording to a comma-separated list of phases (NULL or "" = every phase), so a
