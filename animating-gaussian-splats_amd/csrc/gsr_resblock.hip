@@ -19,7 +19,8 @@
 //                            consecutive chunks, then neighbours merge) into mean and 1 / sqrt(var + eps), and
 //                            blends the running statistics (unbiased variance) as torch does.
 //   k_res_out                out = gelu(bn2(y2) + x), float4 where H % 4 == 0.
-//   k_res_bwd_out            g_s = g_out gelu'(bn2(y2) + x) and per-workgroup column sums of g_s and g_s xhat2.
+//   k_res_bwd_out            g_s = g_out gelu'(bn2(y2) + x) and per-workgroup column sums of g_s and g_s xhat2,
+//                            over column chunks of a power of two (any H).
 //   k_res_colsum             those partials (double) summed in workgroup order: dbeta, dgamma.
 //   k_res_bwd_gemm<NT, ST>   G = BN-backward of (g_in, y) formed into LDS; dW += G^T A accumulated in registers
 //                            over the workgroup's tiles (A = gelu(bn1(y1)) recomputed for stage 2, x for stage
@@ -29,7 +30,15 @@
 //
 // The above is H <= 128, where the whole weight stays in LDS.  128 < H <= 512 runs the k_res_*_wide kernels
 // further down (128-column blocks of the output, k panels of 128, dW in a kernel of its own) with the same
-// mathematics and the same k_res_stats, k_res_out, k_res_colsum and k_res_reduce_w.
+// k_res_stats, k_res_out, k_res_bwd_out, k_res_colsum and k_res_reduce_w.  The two halves differ in their main
+// loops (how the operands reach LDS); the mathematics around them is one set of device helpers: Bn (a column's
+// BatchNorm, forward), BnBack / bn_back_apply (its backward), merge_tile_stats (the forward GEMM's Chan merge)
+// and bwd_r_epilogue / store_stage2_sums (the epilogue of R = G W).  The forward GEMM's store of Y with the
+// wave's (mean, M2), and the final partial store, stay written out in k_res_gemm and k_res_gemm_wide: behind a
+// shared function k_res_gemm<4, false> compiled to 92 VGPRs and lost an occupancy step.  k_res_gemm_wide keeps
+// them out of caution only, so that the H > 128 forward runs the device code it ran before; no cost of the shared
+// form was isolated for it.  On the host one resblock_grid() sizes every grid and the workspace, and gemm<PRO> /
+// stage<STAGE> choose between the halves.
 #include "gsr_common.h"
 #include "gsr_internal.h"
 #include "gsr_mlp.h"
@@ -60,20 +69,114 @@ __device__ inline void chan(double &n, double &mean, double &m2, double nb, doub
     n = tot;
 }
 
-// column i of (mean, invstd, gamma, beta) into cols[0 .. 4 HP), HP floats each, zeros past H
+// one column's BatchNorm
+struct Bn {
+    float mean, invstd, gamma, beta;
+    __device__ float xhat(float v) const { return (v - mean) * invstd; }
+    __device__ float bn_apply(float v) const { return xhat(v) * gamma + beta; }
+};
+// column c of bn, zeros past H
+__device__ inline Bn bn_load(const BnCols &bn, int c, int H) {
+    Bn k = {0.f, 0.f, 0.f, 0.f};
+    if (c < H) {
+        k.mean = bn.mean[c];
+        k.invstd = bn.invstd[c];
+        k.gamma = bn.gamma[c];
+        k.beta = bn.beta[c];
+    }
+    return k;
+}
+// column i into cols[0 .. 4 HP), HP floats per member, and column c back from there
 template <int HP>
 __device__ inline void stage_bn(float *cols, const BnCols &bn, int i, int H) {
-    const bool in = i < H;
-    cols[i] = in ? bn.mean[i] : 0.f;
-    cols[HP + i] = in ? bn.invstd[i] : 0.f;
-    cols[2 * HP + i] = in ? bn.gamma[i] : 0.f;
-    cols[3 * HP + i] = in ? bn.beta[i] : 0.f;
+    const Bn k = bn_load(bn, i, H);
+    cols[i] = k.mean;
+    cols[HP + i] = k.invstd;
+    cols[2 * HP + i] = k.gamma;
+    cols[3 * HP + i] = k.beta;
 }
-
-// gelu(bn(v)) of column c from the staged columns
+template <int HP>
+__device__ inline Bn bn_staged(const float *cols, int c) {
+    return {cols[c], cols[HP + c], cols[2 * HP + c], cols[3 * HP + c]};
+}
 template <int HP>
 __device__ inline float bn_gelu(float v, const float *cols, int c) {
-    return gelu_f(((v - cols[c]) * cols[HP + c]) * cols[2 * HP + c] + cols[3 * HP + c]);
+    return gelu_f(bn_staged<HP>(cols, c).bn_apply(v));
+}
+
+// the BatchNorm backward's constants of one column: mean, invstd, gamma invstd, dbeta / P, dgamma / P
+struct BnBack { float mean, invstd, scale, db, dg; };
+__device__ inline BnBack bn_back(const BnCols &bn, const float *sums, int c, int H, int P) {
+    BnBack k = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c < H) {
+        k.mean = bn.mean[c];
+        k.invstd = bn.invstd[c];
+        k.scale = bn.gamma[c] * k.invstd;
+        k.db = sums[c] / (float)P;
+        k.dg = sums[H + c] / (float)P;
+    }
+    return k;
+}
+__device__ inline float bn_back_apply(const BnBack &k, float g, float y) {
+    const float xh = (y - k.mean) * k.invstd;
+    return k.scale * ((g - k.db) - xh * k.dg);
+}
+
+// The two row halves' (mean, M2) of column c of the tile at row0, st[(2 h, 2 h + 1) * stride + c], merged onto the
+// thread's running (rn, rmean, rm2).
+__device__ inline void merge_tile_stats(double &rn, double &rmean, double &rm2, const float *st, int stride, int c, int row0,
+                                        int P) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        int nv = P - (row0 + h * 32);
+        nv = nv < 0 ? 0 : (nv > 32 ? 32 : nv);
+        chan(rn, rmean, rm2, (double)nv, (double)st[(h * 2 + 0) * stride + c], (double)st[(h * 2 + 1) * stride + c]);
+    }
+}
+
+// Epilogue of R = G W for the wave's 32 x 32 result (rows rbase .., column col).  Stage 2: g_z1 = R gelu'(bn1(y1)),
+// a_in = y1, and this lane's sums of g_z1 and g_z1 xhat1 onto (ps0, ps1).  Stage 1: g_x = R + g_s.  bn1_of() gives
+// bn1 of column col and is asked per row: the narrow kernel reads its staged columns there, which keeps four
+// registers free across the loads (an occupancy step of k_res_bwd_gemm<1, 2>); the wide one holds them anyway.
+template <int STAGE, class BnOf>
+__device__ inline void bwd_r_epilogue(const f32x16 &acc, int rbase, int lane, int col, int H, int P,
+                                      const float *__restrict__ a_in, BnOf bn1_of, const float *__restrict__ g_s,
+                                      float *__restrict__ g_out, double &ps0, double &ps1) {
+    if (col >= H) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = rbase + acc_row(r, lane);
+        if (row >= P) continue;
+        const size_t at = (size_t)row * H + col;
+        if (STAGE == 2) {
+            const Bn bn1 = bn1_of();
+            const float y = a_in[at];
+            const float gz = acc[r] * gelu_grad(bn1.bn_apply(y));
+            g_out[at] = gz;
+            ps0 += (double)gz;
+            ps1 += (double)(gz * bn1.xhat(y));
+        } else {
+            g_out[at] = acc[r] + g_s[at];
+        }
+    }
+}
+// Stage 2's sums of a workgroup: the lanes' (ps0, ps1) of column lc of the workgroup's `stride` columns, through
+// red[2 row halves][2 sums][stride] (the LDS of the operand tiles), to partialS at column col0 + lc.  All threads call it.
+__device__ inline void store_stage2_sums(double ps0, double ps1, double *red, int stride, int lc, int mt, int lane, int H,
+                                         double *__restrict__ partialS, int col0) {
+    const int t = threadIdx.x;
+    ps0 += __shfl_xor(ps0, 32);
+    ps1 += __shfl_xor(ps1, 32);
+    lds_barrier();  // every wave is done with the last tile
+    if (lc < stride && lane < 32) {
+        red[(mt * 2 + 0) * stride + lc] = ps0;
+        red[(mt * 2 + 1) * stride + lc] = ps1;
+    }
+    lds_barrier();
+    if (t < stride && col0 + t < H) {
+        partialS[((size_t)blockIdx.x * 2 + 0) * H + col0 + t] = red[t] + red[2 * stride + t];
+        partialS[((size_t)blockIdx.x * 2 + 1) * H + col0 + t] = red[stride + t] + red[3 * stride + t];
+    }
 }
 
 // prefetch slot q of thread t: row r and column c of the kRows x HP tile
@@ -168,14 +271,7 @@ __global__ __launch_bounds__(kThreads) void k_res_gemm(int P, int H, int tiles, 
             }
         }
         lds_barrier();
-        if (t < H) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                int nv = P - (row0 + h * 32);
-                nv = nv < 0 ? 0 : (nv > 32 ? 32 : nv);
-                chan(rn, rmean, rm2, (double)nv, (double)st[(h * 2 + 0) * HP + t], (double)st[(h * 2 + 1) * HP + t]);
-            }
-        }
+        if (t < H) merge_tile_stats(rn, rmean, rm2, st, HP, t, row0, P);
     }
     if (t < H) {
         double *p = partial + (size_t)blockIdx.x * 3 * H;
@@ -238,40 +334,45 @@ __global__ __launch_bounds__(kEwThreads) void k_res_out(size_t n, int H, const f
     }
 }
 
-// CW: power of two >= H, at most 128; thread t takes column t & (CW - 1) and rows t / CW, + 256 / CW, ...
+// CW: a power of two, at most 256: the columns are walked in chunks of CW (one chunk of the power of two >= H for
+// H <= 128, chunks of 128 above); thread t takes column t & (CW - 1) of each chunk and rows t / CW, + 256 / CW, ...
 __global__ __launch_bounds__(kEwThreads) void k_res_bwd_out(int P, int H, int tiles, int CW, const float *__restrict__ g_out,
                                                             const float *__restrict__ y2, const float *__restrict__ x,
                                                             BnCols bn, float *__restrict__ g_s, double *__restrict__ partial) {
     __shared__ double s_red[2][kEwThreads];
-    const int t = threadIdx.x, c = t & (CW - 1), rl = t / CW, RW = kEwThreads / CW;
-    const bool in = c < H;
-    const float m = in ? bn.mean[c] : 0.f, is = in ? bn.invstd[c] : 0.f, g = in ? bn.gamma[c] : 0.f, b = in ? bn.beta[c] : 0.f;
-    double s0 = 0.0, s1 = 0.0;
-    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int row0 = tile * kRows;
-        for (int r = rl; r < kRows; r += RW) {
-            const int row = row0 + r;
-            if (row < P && in) {
-                const size_t i = (size_t)row * H + c;
-                const float xh = (y2[i] - m) * is;
-                const float gs = g_out[i] * gelu_grad((xh * g + b) + x[i]);
-                g_s[i] = gs;
-                s0 += (double)gs;
-                s1 += (double)(gs * xh);
+    const int t = threadIdx.x, rl = t / CW, RW = kEwThreads / CW;
+    for (int c0 = 0; c0 < H; c0 += CW) {
+        const int c = c0 + (t & (CW - 1));
+        const bool in = c < H;
+        const Bn k = bn_load(bn, c, H);
+        double s0 = 0.0, s1 = 0.0;
+        for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+            const int row0 = tile * kRows;
+            for (int r = rl; r < kRows; r += RW) {
+                const int row = row0 + r;
+                if (row < P && in) {
+                    const size_t i = (size_t)row * H + c;
+                    const float y = y2[i];
+                    const float gs = g_out[i] * gelu_grad(k.bn_apply(y) + x[i]);
+                    g_s[i] = gs;
+                    s0 += (double)gs;
+                    s1 += (double)(gs * k.xhat(y));
+                }
             }
         }
-    }
-    s_red[0][t] = s0;
-    s_red[1][t] = s1;
-    lds_barrier();
-    if (t < CW && in) {
-        double a0 = 0.0, a1 = 0.0;
-        for (int q = 0; q < RW; ++q) {
-            a0 += s_red[0][q * CW + t];
-            a1 += s_red[1][q * CW + t];
+        s_red[0][t] = s0;
+        s_red[1][t] = s1;
+        lds_barrier();
+        if (t < CW && in) {
+            double a0 = 0.0, a1 = 0.0;
+            for (int q = 0; q < RW; ++q) {
+                a0 += s_red[0][q * CW + t];
+                a1 += s_red[1][q * CW + t];
+            }
+            partial[((size_t)blockIdx.x * 2 + 0) * H + c] = a0;
+            partial[((size_t)blockIdx.x * 2 + 1) * H + c] = a1;
         }
-        partial[((size_t)blockIdx.x * 2 + 0) * H + t] = a0;
-        partial[((size_t)blockIdx.x * 2 + 1) * H + t] = a1;
+        lds_barrier();  // s_red is free for the next chunk
     }
 }
 
@@ -324,13 +425,12 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_gemm(int P, int H, int til
             Wn[j * WS + k] = j < H && k < H ? W[(size_t)j * H + k] : 0.f;
         }
     for (int i = t; i < HP; i += kThreads) {
-        const bool in = i < H;
-        const float is = in ? bnG.invstd[i] : 0.f;
-        colsG[i] = in ? bnG.mean[i] : 0.f;
-        colsG[HP + i] = is;
-        colsG[2 * HP + i] = in ? bnG.gamma[i] * is : 0.f;
-        colsG[3 * HP + i] = in ? sums[i] / (float)P : 0.f;
-        colsG[4 * HP + i] = in ? sums[H + i] / (float)P : 0.f;
+        const BnBack k = bn_back(bnG, sums, i, H, P);
+        colsG[i] = k.mean;
+        colsG[HP + i] = k.invstd;
+        colsG[2 * HP + i] = k.scale;
+        colsG[3 * HP + i] = k.db;
+        colsG[4 * HP + i] = k.dg;
         if (STAGE == 2) stage_bn<HP>(colsA, bnA, i, H);
     }
     f32x16 dw[NQ];
@@ -367,8 +467,8 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_gemm(int P, int H, int til
             slot_rc<HP>(t, q, r, c);
             float gy = 0.f, a = 0.f;
             if (row0 + r < P && c < H) {
-                const float xh = (py[q] - colsG[c]) * colsG[HP + c];
-                gy = colsG[2 * HP + c] * ((pg[q] - colsG[3 * HP + c]) - xh * colsG[4 * HP + c]);
+                const BnBack k = {colsG[c], colsG[HP + c], colsG[2 * HP + c], colsG[3 * HP + c], colsG[4 * HP + c]};
+                gy = bn_back_apply(k, pg[q], py[q]);
                 a = pa[q];
                 if (STAGE == 2 && want_w) a = bn_gelu<HP>(a, colsA, c);
             }
@@ -398,23 +498,8 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_gemm(int P, int H, int til
             const float *wb = Wn + (lane >> 5) * WS + nt * 32 + (lane & 31);
             for (int j = 0; j < KP; j += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[j], wb[j * WS], acc, 0, 0, 0);
             const int col = nt * 32 + (lane & 31);
-            if (col < H) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = row0 + mt * 32 + acc_row(r, lane);
-                    if (row >= P) continue;
-                    const size_t at = (size_t)row * H + col;
-                    if (STAGE == 2) {
-                        const float xh = (a_in[at] - colsA[col]) * colsA[HP + col];
-                        const float gz = acc[r] * gelu_grad(xh * colsA[2 * HP + col] + colsA[3 * HP + col]);
-                        g_out[at] = gz;
-                        ps0 += (double)gz;
-                        ps1 += (double)(gz * xh);
-                    } else {
-                        g_out[at] = acc[r] + g_s[at];
-                    }
-                }
-            }
+            bwd_r_epilogue<STAGE>(acc, row0 + mt * 32, lane, col, H, P, a_in, [&] { return bn_staged<HP>(colsA, col); }, g_s,
+                                  g_out, ps0, ps1);
         }
     }
 
@@ -431,21 +516,8 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_gemm(int P, int H, int til
             }
         }
     }
-    if (STAGE == 2 && want_g) {
-        double *red = (double *)s_lds;  // 2 row halves x 2 sums x HP, over the G tile
-        ps0 += __shfl_xor(ps0, 32);
-        ps1 += __shfl_xor(ps1, 32);
-        lds_barrier();  // every wave is done with the last tile
-        if (nt < NT && lane < 32) {
-            red[(mt * 2 + 0) * HP + nt * 32 + lane] = ps0;
-            red[(mt * 2 + 1) * HP + nt * 32 + lane] = ps1;
-        }
-        lds_barrier();
-        if (t < H) {
-            partialS[((size_t)blockIdx.x * 2 + 0) * H + t] = red[t] + red[2 * HP + t];
-            partialS[((size_t)blockIdx.x * 2 + 1) * H + t] = red[HP + t] + red[3 * HP + t];
-        }
-    }
+    if (STAGE == 2 && want_g)  // red over the G tile
+        store_stage2_sums(ps0, ps1, (double *)s_lds, HP, nt * 32 + (lane & 31), mt, lane, H, partialS, 0);
 }
 
 __global__ __launch_bounds__(256) void k_res_reduce_w(int n, int nb, const float *__restrict__ partial, float *__restrict__ dW) {
@@ -466,7 +538,6 @@ __global__ __launch_bounds__(256) void k_res_reduce_w(int n, int nb, const float
 //
 //   k_res_gemm_wide<PRO>     k_res_gemm for column block blockIdx.y; a column belongs to one block, so the
 //                            statistics partials keep their (workgroup along the rows, 3, H) layout.
-//   k_res_bwd_out_wide       k_res_bwd_out over column chunks of 128.
 //   k_res_bwd_r_wide<ST>     R = G W for column block blockIdx.y with the epilogues of k_res_bwd_gemm.
 //   k_res_bwd_w_wide<ST>     dW = G^T A: workgroup (row group, 128 x 128 block of dW) forms the G and A panels
 //                            of the block's columns per 64-row tile, each wave two 32 x 32 accumulators; one
@@ -485,24 +556,6 @@ constexpr int kNW = kPanel * kPanel / kThreads;  // ... of a 128 x 128 weight pa
 __device__ inline float load_clamped(const float *base, int r, int rows, int H, int c, bool cin) {
     return base[(unsigned)((r < rows ? r : rows - 1) * H + (cin ? c : 0))];
 }
-
-// the BatchNorm backward's constants of one column: mean, invstd, gamma invstd, dbeta / P, dgamma / P
-struct BnBack { float mean, invstd, scale, db, dg; };
-__device__ inline BnBack bn_back(const BnCols &bn, const float *sums, int c, int H, int P) {
-    BnBack k = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (c < H) {
-        k.mean = bn.mean[c];
-        k.invstd = bn.invstd[c];
-        k.scale = bn.gamma[c] * k.invstd;
-        k.db = sums[c] / (float)P;
-        k.dg = sums[H + c] / (float)P;
-    }
-    return k;
-}
-__device__ inline float bn_back_apply(const BnBack &k, float g, float y) {
-    const float xh = (y - k.mean) * k.invstd;
-    return k.scale * ((g - k.db) - xh * k.dg);
-}
 }  // namespace
 
 template <bool PRO>
@@ -518,7 +571,8 @@ __global__ __launch_bounds__(kThreads) void k_res_gemm_wide(int P, int H, int ti
     const int pc = t & (kPanel - 1), pr = t >> 7;
     const bool live = col0 + nt * 32 < H;  // this wave's column tile holds a column of the matrix
 
-    float px[kNX], pw[kNW], bm = 0.f, bi = 0.f, bg = 0.f, bb = 0.f;
+    float px[kNX], pw[kNW];
+    Bn kb = {0.f, 0.f, 0.f, 0.f};  // the prologue's BatchNorm of the prefetched panel's column
     auto fetch = [&](int tile, int kp) {
         const int k = kp * kPanel + pc;
         const bool kin = k < H;
@@ -528,7 +582,7 @@ __global__ __launch_bounds__(kThreads) void k_res_gemm_wide(int P, int H, int ti
         for (int q = 0; q < kNX; ++q) px[q] = load_clamped(xt, pr + q * kRowStep, rows, H, k, kin);
 #pragma unroll
         for (int q = 0; q < kNW; ++q) pw[q] = load_clamped(wt, pr + q * kRowStep, cols, H, k, kin);
-        if (PRO && kin) { bm = bn.mean[k]; bi = bn.invstd[k]; bg = bn.gamma[k]; bb = bn.beta[k]; }
+        if (PRO && kin) kb = bn_load(bn, k, H);
     };
     if ((int)blockIdx.x < tiles) fetch(blockIdx.x, 0);
 
@@ -547,7 +601,7 @@ __global__ __launch_bounds__(kThreads) void k_res_gemm_wide(int P, int H, int ti
             for (int q = 0; q < kNX; ++q) {
                 const int r = pr + q * kRowStep;
                 float v = px[q];
-                if (PRO) v = gelu_f(((v - bm) * bi) * bg + bb);
+                if (PRO) v = gelu_f(kb.bn_apply(v));
                 Xs[r * kPS + pc] = kin ? v : 0.f;
             }
 #pragma unroll
@@ -589,63 +643,13 @@ __global__ __launch_bounds__(kThreads) void k_res_gemm_wide(int P, int H, int ti
             }
         }
         lds_barrier();
-        if (t < kPanel && col0 + t < H) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                int nv = P - (row0 + h * 32);
-                nv = nv < 0 ? 0 : (nv > 32 ? 32 : nv);
-                chan(rn, rmean, rm2, (double)nv, (double)st[(h * 2 + 0) * kPanel + t], (double)st[(h * 2 + 1) * kPanel + t]);
-            }
-        }
+        if (t < kPanel && col0 + t < H) merge_tile_stats(rn, rmean, rm2, st, kPanel, t, row0, P);
     }
     if (t < kPanel && col0 + t < H) {
         double *p = partial + (size_t)blockIdx.x * 3 * H + col0 + t;
         p[0] = rn;
         p[H] = rmean;
         p[2 * H] = rm2;
-    }
-}
-
-// thread t takes column (t & 127) of each 128-column chunk and rows t >> 7, + 2, ...
-__global__ __launch_bounds__(kEwThreads) void k_res_bwd_out_wide(int P, int H, int tiles, const float *__restrict__ g_out,
-                                                                 const float *__restrict__ y2, const float *__restrict__ x,
-                                                                 BnCols bn, float *__restrict__ g_s,
-                                                                 double *__restrict__ partial) {
-    __shared__ double s_red[2][kEwThreads];
-    constexpr int RW = kEwThreads / kPanel;
-    const int t = threadIdx.x, rl = t >> 7;
-    for (int c0 = 0; c0 < H; c0 += kPanel) {
-        const int c = c0 + (t & (kPanel - 1));
-        const bool in = c < H;
-        const float m = in ? bn.mean[c] : 0.f, is = in ? bn.invstd[c] : 0.f, g = in ? bn.gamma[c] : 0.f, b = in ? bn.beta[c] : 0.f;
-        double s0 = 0.0, s1 = 0.0;
-        for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-            const int row0 = tile * kRows;
-            for (int r = rl; r < kRows; r += RW) {
-                const int row = row0 + r;
-                if (row < P && in) {
-                    const size_t i = (size_t)row * H + c;
-                    const float xh = (y2[i] - m) * is;
-                    const float gs = g_out[i] * gelu_grad((xh * g + b) + x[i]);
-                    g_s[i] = gs;
-                    s0 += (double)gs;
-                    s1 += (double)(gs * xh);
-                }
-            }
-        }
-        s_red[0][t] = s0;
-        s_red[1][t] = s1;
-        lds_barrier();
-        if (t < kPanel && in) {
-            double a0 = 0.0, a1 = 0.0;
-            for (int q = 0; q < RW; ++q) {
-                a0 += s_red[0][q * kPanel + t];
-                a1 += s_red[1][q * kPanel + t];
-            }
-            partial[((size_t)blockIdx.x * 2 + 0) * H + c] = a0;
-            partial[((size_t)blockIdx.x * 2 + 1) * H + c] = a1;
-        }
-        lds_barrier();  // s_red is free for the next chunk
     }
 }
 
@@ -666,9 +670,8 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_r_wide(int P, int H, int t
     const int lc = nt * 32 + (lane & 31), col = col0 + lc;
     const bool live = col0 + nt * 32 < H;
 
-    float am = 0.f, ai = 0.f, ag = 0.f, ab = 0.f;  // stage 2: bn1 of this lane's output column
-    if (STAGE == 2 && col < H) { am = bnA.mean[col]; ai = bnA.invstd[col]; ag = bnA.gamma[col]; ab = bnA.beta[col]; }
-    double ps0 = 0.0, ps1 = 0.0;  // stage 2: this lane's rows of column col
+    const Bn bn1 = bn_load(bnA, col, H);  // bn1 of this lane's output column; stage 1 does not use it and the loads go
+    double ps0 = 0.0, ps1 = 0.0;          // stage 2: this lane's rows of column col
 
     float pg[kNX], py[kNX], pw[kNW];
     BnBack kb = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -718,39 +721,9 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_r_wide(int P, int H, int t
                 for (int j = 0; j < jn; j += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[j], wb[j * kPS], acc, 0, 0, 0);
             }
         }
-        if (col < H) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row0 + mt * 32 + acc_row(r, lane);
-                if (row >= P) continue;
-                const size_t at = (size_t)row * H + col;
-                if (STAGE == 2) {
-                    const float xh = (a_in[at] - am) * ai;
-                    const float gz = acc[r] * gelu_grad(xh * ag + ab);
-                    g_out[at] = gz;
-                    ps0 += (double)gz;
-                    ps1 += (double)(gz * xh);
-                } else {
-                    g_out[at] = acc[r] + g_s[at];
-                }
-            }
-        }
+        bwd_r_epilogue<STAGE>(acc, row0 + mt * 32, lane, col, H, P, a_in, [&] { return bn1; }, g_s, g_out, ps0, ps1);
     }
-    if (STAGE == 2) {
-        double *red = (double *)s_lds;  // 2 row halves x 2 sums x kPanel, over the G panel
-        ps0 += __shfl_xor(ps0, 32);
-        ps1 += __shfl_xor(ps1, 32);
-        lds_barrier();  // every wave is done with the last panel
-        if (lane < 32) {
-            red[(mt * 2 + 0) * kPanel + lc] = ps0;
-            red[(mt * 2 + 1) * kPanel + lc] = ps1;
-        }
-        lds_barrier();
-        if (t < kPanel && col0 + t < H) {
-            partialS[((size_t)blockIdx.x * 2 + 0) * H + col0 + t] = red[t] + red[2 * kPanel + t];
-            partialS[((size_t)blockIdx.x * 2 + 1) * H + col0 + t] = red[kPanel + t] + red[3 * kPanel + t];
-        }
-    }
+    if (STAGE == 2) store_stage2_sums(ps0, ps1, (double *)s_lds, kPanel, lc, mt, lane, H, partialS, col0);  // red over the G panel
 }
 
 // grid (row groups, CB * CB blocks of dW): block blockIdx.y = jb * CB + kb is dW[128 jb .., 128 kb ..]
@@ -767,8 +740,7 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_w_wide(int P, int H, int t
     const int pc = t & (kPanel - 1), pr = t >> 7;
     const int cj = j0 + pc, ck = k0 + pc;
     const BnBack kb = bn_back(bnG, sums, cj, H, P);
-    float am = 0.f, ai = 0.f, ag = 0.f, ab = 0.f;  // stage 2: bn1 of column ck
-    if (STAGE == 2 && ck < H) { am = bnA.mean[ck]; ai = bnA.invstd[ck]; ag = bnA.gamma[ck]; ab = bnA.beta[ck]; }
+    const Bn bn1 = bn_load(bnA, ck, H);  // bn1 of column ck; stage 1 does not use it and the loads go
 
     f32x16 dw[2];  // 32 x 32 tiles w and w + 8 of the block's 4 x 4
 #pragma unroll
@@ -798,7 +770,7 @@ __global__ __launch_bounds__(kThreads) void k_res_bwd_w_wide(int P, int H, int t
             const int r = pr + q * kRowStep;
             const bool rin = row0 + r < P;
             float a = pa[q];
-            if (STAGE == 2) a = gelu_f(((a - am) * ai) * ag + ab);
+            if (STAGE == 2) a = gelu_f(bn1.bn_apply(a));
             Gs[r * kPS + pc] = rin && cj < H ? bn_back_apply(kb, pg[q], py[q]) : 0.f;
             As[r * kPS + pc] = rin && ck < H ? a : 0.f;
         }
@@ -841,79 +813,72 @@ size_t bwd_lds(int nt) {
     return sizeof(float) * ((size_t)2 * tile + (tile & 1) + 9 * HP + (size_t)HP * (HP + 1));
 }
 
-template <bool PRO>
-hipError_t gemm(int nb, int P, int H, const float *X, const float *W, const BnCols &bn, float *Y, double *partial,
-                hipStream_t s) {
-    return dispatch_tiles(res_nt(H), [&](auto n) {
-        constexpr int NT = decltype(n)::value;
-        return launch_lds(k_res_gemm<NT, PRO>, nb, kThreads, fwd_lds(NT), s, P, H, div_up(P, kRows), X, W, bn, Y, partial);
-    });
-}
-
-template <int STAGE>
-hipError_t bwd_gemm(int nb, int P, int H, const float *g_in, const float *yn, const BnCols &bnG, const float *sums,
-                    const float *a_in, const BnCols &bnA, const float *W, const float *g_s, float *g_out, float *partialW,
-                    double *partialS, hipStream_t s) {
-    return dispatch_tiles(res_nt(H), [&](auto n) {
-        constexpr int NT = decltype(n)::value;
-        return launch_lds(k_res_bwd_gemm<NT, STAGE>, nb, kThreads, bwd_lds(NT), s, P, H, div_up(P, kRows), g_in, yn, bnG,
-                          sums, a_in, bnA, W, g_s, g_out, partialW, partialS);
-    });
-}
-
-// H <= 64: two workgroups fit a CU's LDS
-int resblock_blocks(int P, int H, int max_blocks) {
-    return persistent_blocks(P, kRows, max_blocks, kResblockAutoBlocks * (H <= 64 ? 2 : 1));
-}
-int resblock_out_blocks(int P, int max_blocks) { return persistent_blocks(P, kRows, max_blocks, kOutBlocks); }
-
-// H > 128.  Workgroups along the rows of the forward and R = G W kernels: with the column blocks about one per CU
-// (their LDS admits no second).  Row groups of dW = G^T A: with the CB x CB blocks of dW about one workgroup per
-// CU as well, which bounds the dW partials by kResblockAutoBlocks x 128 x 128 floats (16 MB) for every H and P.
-bool wide(int H) { return H > kResblockNarrowH; }
-int wide_cb(int H) { return div_up(H, kPanel); }
-int wide_blocks(int P, int H, int max_blocks) {
-    return persistent_blocks(P, kRows, max_blocks, kResblockAutoBlocks / wide_cb(H));
-}
-int wide_groups(int P, int H, int max_blocks) {
-    return persistent_blocks(P, kRows, max_blocks, kResblockAutoBlocks / (wide_cb(H) * wide_cb(H)));
-}
 constexpr size_t kWideFwdLds = sizeof(float) * ((size_t)kRows * kPS + (size_t)kPanel * kPS + 4 * kPanel);
 constexpr size_t kWideRLds = sizeof(float) * ((size_t)kRows * kPS + (size_t)kPanel * kPS);
 constexpr size_t kWideWLds = sizeof(float) * ((size_t)2 * kRows * kPS);
 
+bool wide(int H) { return H > kResblockNarrowH; }
+int wide_cb(int H) { return div_up(H, kPanel); }  // column blocks; 1 for H <= 128
+
+// The grids of one (P, H, max_blocks), which the workspace's carving and both launchers share.
+//   nb  workgroups along the rows of the forward and backward GEMM kernels.  H <= 64: two fit a CU's LDS.  H > 128:
+//       with the CB column blocks about one per CU (their LDS admits no second).
+//   ng  row groups of dW = G^T A, one partial each.  H <= 128: dW comes from the same workgroups, ng = nb.  H > 128:
+//       with the CB x CB blocks of dW about one workgroup per CU as well, which bounds the dW partials by
+//       kResblockAutoBlocks x 128 x 128 floats (16 MB) for every H and P.
+//   no  workgroups of k_res_bwd_out.
+struct ResblockGrid { int nb, ng, no; };
+ResblockGrid resblock_grid(int P, int H, int max_blocks) {
+    const int cb = wide_cb(H), per_cu = H <= 64 ? 2 : 1;
+    return {persistent_blocks(P, kRows, max_blocks, kResblockAutoBlocks * per_cu / cb),
+            persistent_blocks(P, kRows, max_blocks, kResblockAutoBlocks * per_cu / (cb * cb)),
+            persistent_blocks(P, kRows, max_blocks, kOutBlocks)};
+}
+
+// Y = A W^T and its statistics partials, A = X or gelu(bn(X))
 template <bool PRO>
-hipError_t gemm_wide(int nb, int P, int H, const float *X, const float *W, const BnCols &bn, float *Y, double *partial,
-                     hipStream_t s) {
-    return launch_lds(k_res_gemm_wide<PRO>, dim3(nb, wide_cb(H)), kThreads, kWideFwdLds, s, P, H, div_up(P, kRows), X, W,
-                      bn, Y, partial);
+hipError_t gemm(const ResblockGrid &g, int P, int H, const float *X, const float *W, const BnCols &bn, float *Y,
+                double *partial, hipStream_t s) {
+    const int tiles = div_up(P, kRows);
+    if (wide(H))
+        return launch_lds(k_res_gemm_wide<PRO>, dim3(g.nb, wide_cb(H)), kThreads, kWideFwdLds, s, P, H, tiles, X, W, bn, Y,
+                          partial);
+    return dispatch_tiles(res_nt(H), [&](auto n) {
+        constexpr int NT = decltype(n)::value;
+        return launch_lds(k_res_gemm<NT, PRO>, g.nb, kThreads, fwd_lds(NT), s, P, H, tiles, X, W, bn, Y, partial);
+    });
 }
 
 // stage STAGE of the backward: R = G W into g_out (unless NULL) and dW into dW (unless NULL)
 template <int STAGE>
-hipError_t bwd_wide(int nb, int ng, int P, int H, const float *g_in, const float *yn, const BnCols &bnG, const float *sums,
-                    const float *a_in, const BnCols &bnA, const float *W, const float *g_s, float *g_out, float *partialW,
-                    float *dW, double *partialS, hipStream_t s) {
+hipError_t stage(const ResblockGrid &g, int P, int H, const float *g_in, const float *yn, const BnCols &bnG,
+                 const float *sums, const float *a_in, const BnCols &bnA, const float *W, const float *g_s, float *g_out,
+                 float *partialW, float *dW, double *partialS, hipStream_t s) {
     const int tiles = div_up(P, kRows), cb = wide_cb(H);
-    if (g_out) {
-        hipError_t e = launch_lds(k_res_bwd_r_wide<STAGE>, dim3(nb, cb), kThreads, kWideRLds, s, P, H, tiles, g_in, yn, bnG,
-                                  sums, a_in, bnA, W, g_s, g_out, partialS);
-        if (e != hipSuccess) return e;
+    hipError_t e = hipSuccess;
+    if (!wide(H)) {
+        e = dispatch_tiles(res_nt(H), [&](auto n) {
+            constexpr int NT = decltype(n)::value;
+            return launch_lds(k_res_bwd_gemm<NT, STAGE>, g.nb, kThreads, bwd_lds(NT), s, P, H, tiles, g_in, yn, bnG, sums,
+                              a_in, bnA, W, g_s, g_out, dW ? partialW : nullptr, partialS);
+        });
+    } else {
+        if (g_out)
+            e = launch_lds(k_res_bwd_r_wide<STAGE>, dim3(g.nb, cb), kThreads, kWideRLds, s, P, H, tiles, g_in, yn, bnG, sums,
+                           a_in, bnA, W, g_s, g_out, partialS);
+        if (e == hipSuccess && dW)
+            e = launch_lds(k_res_bwd_w_wide<STAGE>, dim3(g.ng, cb * cb), kThreads, kWideWLds, s, P, H, tiles, cb, g_in, yn,
+                           bnG, sums, a_in, bnA, partialW);
     }
-    if (dW) {
-        hipError_t e = launch_lds(k_res_bwd_w_wide<STAGE>, dim3(ng, cb * cb), kThreads, kWideWLds, s, P, H, tiles, cb, g_in,
-                                  yn, bnG, sums, a_in, bnA, partialW);
-        if (e != hipSuccess) return e;
-        k_res_reduce_w<<<div_up(H * H, 256), 256, 0, s>>>(H * H, ng, partialW, dW);
-    }
+    if (e != hipSuccess) return e;
+    if (dW) k_res_reduce_w<<<div_up(H * H, 256), 256, 0, s>>>(H * H, g.ng, partialW, dW);
     return hipGetLastError();
 }
 }  // namespace
 
 ResblockWorkspace::ResblockWorkspace(int P, int H, int max_blocks, bool backward) {
-    const size_t nb = (size_t)(wide(H) ? wide_blocks(P, H, max_blocks) : resblock_blocks(P, H, max_blocks));
-    const size_t ng = wide(H) ? (size_t)wide_groups(P, H, max_blocks) : nb;  // dW partials
-    const size_t no = (size_t)resblock_out_blocks(P, max_blocks);
+    const ResblockGrid g = resblock_grid(P, H, max_blocks);
+    const size_t nb = (size_t)g.nb, ng = (size_t)g.ng, no = (size_t)g.no;
     const size_t h = (size_t)H, ph = (size_t)P * h;
     size_t o = 0;
     partial_s = o; o = align256(o + sizeof(double) * 3 * h * (nb > no ? nb : no));
@@ -933,17 +898,16 @@ hipError_t launch_resblock_fwd(int P, int H, const float *x, const float *W1, co
                                float *running_mean2, float *running_var2, char *ws, int max_blocks, float *y1, float *y2,
                                float *out, float *stats, hipStream_t s) {
     const ResblockWorkspace L(P, H, max_blocks, false);
-    const int nb = wide(H) ? wide_blocks(P, H, max_blocks) : resblock_blocks(P, H, max_blocks);
+    const ResblockGrid g = resblock_grid(P, H, max_blocks);
     double *partial = (double *)(ws + L.partial_s);
     const BnCols none = {nullptr, nullptr, nullptr, nullptr};
     const BnCols bn1 = {stats, stats + H, gamma1, beta1}, bn2 = {stats + 2 * H, stats + 3 * H, gamma2, beta2};
-    hipError_t e = wide(H) ? gemm_wide<false>(nb, P, H, x, W1, none, y1, partial, s)
-                           : gemm<false>(nb, P, H, x, W1, none, y1, partial, s);
+    hipError_t e = gemm<false>(g, P, H, x, W1, none, y1, partial, s);
     if (e != hipSuccess) return e;
-    k_res_stats<<<H, 64, 0, s>>>(P, H, nb, partial, eps1, momentum1, stats, stats + H, running_mean1, running_var1);
-    e = wide(H) ? gemm_wide<true>(nb, P, H, y1, W2, bn1, y2, partial, s) : gemm<true>(nb, P, H, y1, W2, bn1, y2, partial, s);
+    k_res_stats<<<H, 64, 0, s>>>(P, H, g.nb, partial, eps1, momentum1, stats, stats + H, running_mean1, running_var1);
+    e = gemm<true>(g, P, H, y1, W2, bn1, y2, partial, s);
     if (e != hipSuccess) return e;
-    k_res_stats<<<H, 64, 0, s>>>(P, H, nb, partial, eps2, momentum2, stats + 2 * H, stats + 3 * H, running_mean2, running_var2);
+    k_res_stats<<<H, 64, 0, s>>>(P, H, g.nb, partial, eps2, momentum2, stats + 2 * H, stats + 3 * H, running_mean2, running_var2);
     const size_t n = (size_t)P * H;
     const bool vec = H % 4 == 0 && aligned16(y2) && aligned16(x) && aligned16(out) && aligned16(stats) &&
                      aligned16(gamma2) && aligned16(beta2);
@@ -961,47 +925,26 @@ hipError_t launch_resblock_bwd(int P, int H, const float *x, const float *y1, co
                                float *dx, float *dW1, float *dgamma1, float *dbeta1, float *dW2, float *dgamma2,
                                float *dbeta2, hipStream_t s) {
     const ResblockWorkspace L(P, H, max_blocks, true);
-    const int nb = resblock_blocks(P, H, max_blocks), no = resblock_out_blocks(P, max_blocks), tiles = div_up(P, kRows);
+    const ResblockGrid g = resblock_grid(P, H, max_blocks);
     double *partial_s = (double *)(ws + L.partial_s);
     float *partial_w = (float *)(ws + L.partial_w), *sums = (float *)(ws + L.sums);
     float *g_s = (float *)(ws + L.g_s), *g_z1 = (float *)(ws + L.g_z1);
     const BnCols bn1 = {stats, stats + H, gamma1, beta1}, bn2 = {stats + 2 * H, stats + 3 * H, gamma2, beta2};
     const bool below = dx || dW1 || dgamma1 || dbeta1;  // anything past a1
-    if (wide(H)) {
-        const int nw = wide_blocks(P, H, max_blocks), ng = wide_groups(P, H, max_blocks);
-        k_res_bwd_out_wide<<<no, kEwThreads, 0, s>>>(P, H, tiles, g_out, y2, x, bn2, g_s, partial_s);
-        k_res_colsum<<<H, 64, 0, s>>>(H, no, partial_s, sums, dbeta2, dgamma2);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (dW2 || below) {
-            e = bwd_wide<2>(nw, ng, P, H, g_s, y2, bn2, sums, y1, bn1, W2, nullptr, below ? g_z1 : nullptr, partial_w, dW2,
-                            partial_s, s);
-            if (e != hipSuccess) return e;
-            if (below) k_res_colsum<<<H, 64, 0, s>>>(H, nw, partial_s, sums + 2 * H, dbeta1, dgamma1);
-        }
-        if (dx || dW1) {
-            e = bwd_wide<1>(nw, ng, P, H, g_z1, y1, bn1, sums + 2 * H, x, bn1, W1, g_s, dx, partial_w, dW1, nullptr, s);
-            if (e != hipSuccess) return e;
-        }
-        return hipGetLastError();
-    }
-    int CW = 8;
-    while (CW < H) CW <<= 1;
-    k_res_bwd_out<<<no, kEwThreads, 0, s>>>(P, H, tiles, CW, g_out, y2, x, bn2, g_s, partial_s);
-    k_res_colsum<<<H, 64, 0, s>>>(H, no, partial_s, sums, dbeta2, dgamma2);
+    int CW = 8;  // k_res_bwd_out's column chunk: the power of two >= H, 128 for H > 128
+    while (CW < H && CW < kPanel) CW <<= 1;
+    k_res_bwd_out<<<g.no, kEwThreads, 0, s>>>(P, H, div_up(P, kRows), CW, g_out, y2, x, bn2, g_s, partial_s);
+    k_res_colsum<<<H, 64, 0, s>>>(H, g.no, partial_s, sums, dbeta2, dgamma2);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (dW2 || below) {
-        e = bwd_gemm<2>(nb, P, H, g_s, y2, bn2, sums, y1, bn1, W2, nullptr, below ? g_z1 : nullptr,
-                        dW2 ? partial_w : nullptr, partial_s, s);
+        e = stage<2>(g, P, H, g_s, y2, bn2, sums, y1, bn1, W2, nullptr, below ? g_z1 : nullptr, partial_w, dW2, partial_s, s);
         if (e != hipSuccess) return e;
-        if (dW2) k_res_reduce_w<<<div_up(H * H, 256), 256, 0, s>>>(H * H, nb, partial_w, dW2);
-        if (below) k_res_colsum<<<H, 64, 0, s>>>(H, nb, partial_s, sums + 2 * H, dbeta1, dgamma1);
+        if (below) k_res_colsum<<<H, 64, 0, s>>>(H, g.nb, partial_s, sums + 2 * H, dbeta1, dgamma1);
     }
     if (dx || dW1) {
-        e = bwd_gemm<1>(nb, P, H, g_z1, y1, bn1, sums + 2 * H, x, bn1, W1, g_s, dx, dW1 ? partial_w : nullptr, nullptr, s);
+        e = stage<1>(g, P, H, g_z1, y1, bn1, sums + 2 * H, x, bn1, W1, g_s, dx, partial_w, dW1, nullptr, s);
         if (e != hipSuccess) return e;
-        if (dW1) k_res_reduce_w<<<div_up(H * H, 256), 256, 0, s>>>(H * H, nb, partial_w, dW1);
     }
     return hipGetLastError();
 }
